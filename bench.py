@@ -24,6 +24,11 @@ owns its own batches (weak scaling, no data-path collective in the timed region)
 built on rank 0 and broadcast once over RCCL (setup, untimed).  `--selftest` runs the same
 launcher and rank logic on the CPU with gloo and no HIP call (the CPU test of the launcher).
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline needs and no more: traces and
+handles, W untimed steps, K timed steps, `--dump-outputs DIR` (what the last timed step computed, as
+.npy files: see dump_outputs) and the line.  Everything below is measured only with `--full`, which
+also writes the full record file.
+
 Roofline: the dominant kernel (the headline path's classify launch) is timed with HIP events around
 each launch in a separate single-stream pass (grouping deferred past the stop event);
 its HBM traffic is measured in the same invocation by two rocprofv3 --pmc passes (FETCH_SIZE,
@@ -82,6 +87,8 @@ MULTI_STREAMS = int(os.environ.get("NBG_BENCH_MULTI_STREAMS", "2"))
 IMIX_MULTI_K = int(os.environ.get("NBG_BENCH_IMIX_MULTI_K", "8"))
 IMIX_MULTI_STREAMS = int(os.environ.get("NBG_BENCH_IMIX_MULTI_STREAMS", "2"))
 SEED = 0x4E42474D41474C56
+# --dump-outputs: per batch, backend[] / perm[] at DUMP_SAMPLE seeded packet indices, the MACs of DUMP_PKTS
+DUMP_SEED, DUMP_SAMPLE, DUMP_PKTS = 20240607, 1 << 18, 1 << 15
 # algorithmic bytes per packet of the classify kernel per variant:
 #   in place: 64 B packet read + 12 B MAC write + 2 B backend write
 #   records:  64 B packet read + 12 B dense MAC record + 2 B backend
@@ -209,16 +216,20 @@ def compact_line(full: dict) -> dict:
     return line
 
 
-def emit_line(full: dict) -> None:
-    """Write the full record to FULL_RECORD and print the compact line (one line, <= LINE_LIMIT bytes:
-    a longer one would be cut by the driver's stdout tail, so fail loudly instead)."""
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(FULL_RECORD)), exist_ok=True)
-        with open(FULL_RECORD, "w") as f:
-            json.dump(full, f, indent=1)
-    except OSError as e:
-        log(f"bench: could not write the full record {FULL_RECORD}: {e}")
+def emit_line(full: dict, record: bool = True) -> None:
+    """Write the full record to FULL_RECORD (record=False, a run without --full: no file) and print the
+    compact line (one line, <= LINE_LIMIT bytes: a longer one would be cut by a reader that keeps only
+    the tail of stdout, so fail loudly instead)."""
+    if record:
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(FULL_RECORD)), exist_ok=True)
+            with open(FULL_RECORD, "w") as f:
+                json.dump(full, f, indent=1)
+        except OSError as e:
+            log(f"bench: could not write the full record {FULL_RECORD}: {e}")
     line = compact_line(full)
+    if not record:
+        del line["full_record"]
     s = json.dumps(line, separators=(",", ":"))
     if len(s) > LINE_LIMIT:
         log(f"bench: the JSON line is {len(s)} bytes, above the {LINE_LIMIT}-byte limit")
@@ -695,7 +706,7 @@ def launch(args, argv) -> int:
         t0 = time.time()
         line["e2e"] = e2e_block()
         log(f"bench: end-to-end pass {time.time() - t0:.0f}s")
-    emit_line(line)
+    emit_line(line, record=args.full)
     return 0
 
 
@@ -759,7 +770,7 @@ def run_rank(args) -> None:
     host_bufs, dbufs = [], []
     for b in range(1 if args.selftest else N_BATCHES):
         buf, _, _ = nb.make_trace(BATCH, 0, seed=shard_seed(rank, b))
-        if rank == 0 and world == 1:
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
             host_bufs.append(buf.copy())
         dbufs.append(torch.from_numpy(buf).to(dev) if gpu else torch.from_numpy(buf))
     log(f"[rank {rank}] traces ready in {time.time() - t0:.1f}s")
@@ -1739,6 +1750,38 @@ def run_rank(args) -> None:
                          "classify launch, then one hist / scan / group launch over all batches, per-batch outputs), "
                          f"{ms} streams with distinct inputs; classify_us_per_batch from the multi launch timed alone")}
 
+    def dump_outputs(path, headline, steps):
+        """--dump-outputs: what the headline's last timed step left on the device, as a caller of that
+        path receives it, one set of .npy files per batch b of the step: b<b>_counts (all N_BACKENDS + 1
+        group sizes), b<b>_backend and b<b>_perm (the entries at DUMP_SAMPLE fixed, seeded packet
+        indices) and b<b>_macs (the first 12 bytes, rewritten in place, of DUMP_PKTS fixed, seeded
+        packets), float32 (perm float64); 38 MB in all.  The inputs are seeded and the same arguments swap
+        every batch the same number of times, so two builds run alike write comparable files."""
+        if headline == "multi":
+            sets = {b: m_outs[b] for b in range(N_BATCHES)}
+        elif headline == "launch":  # 2 x S output sets: a set's last writer within the step owns it
+            owner = {}
+            for q in range(BATCHES_PER_STEP):
+                g = (steps - 1) * BATCHES_PER_STEP + q
+                owner[(g % S, (g // S) & 1)] = g % N_BATCHES
+            sets = {b: tuple(outs[j][par][k] for k in ("backend", "perm", "counts")) for (j, par), b in owner.items()}
+        else:
+            raise SystemExit(f"bench: --dump-outputs does not cover the headline path {headline!r}")
+        os.makedirs(path, exist_ok=True)
+        rs = np.random.RandomState(DUMP_SEED)
+        idx = torch.from_numpy(np.sort(rs.choice(BATCH, DUMP_SAMPLE, replace=False))).to(dev)
+        pidx = torch.from_numpy(np.sort(rs.choice(BATCH, DUMP_PKTS, replace=False))).to(dev)
+        total = 0
+        for b, (be, pm, ct) in sorted(sets.items()):
+            arrs = {"backend": be.view(torch.int16)[idx].cpu().numpy().view(np.uint16).astype(np.float32),
+                    "perm": pm.view(torch.int32)[idx].cpu().numpy().view(np.uint32).astype(np.float64),
+                    "counts": ct.view(torch.int32).cpu().numpy().view(np.uint32).astype(np.float32),
+                    "macs": dbufs[b].view(BATCH, SLOT)[pidx, :12].cpu().numpy().astype(np.float32)}
+            for name, a in arrs.items():
+                np.save(os.path.join(path, f"b{b}_{name}.npy"), a)
+                total += a.nbytes
+        log(f"[rank {rank}] --dump-outputs: {4 * len(sets)} arrays, {total / 1e6:.1f} MB in {path}")
+
     if args.pmc_child:  # under rocprofv3 --pmc: each variant's launches in a fixed order, one stream
         st = sts[0]
         for v in PMC_ORDER:
@@ -1810,6 +1853,10 @@ def run_rank(args) -> None:
     per_rank_s = gather_floats(elapsed_rank)
     elapsed = max(per_rank_s)
     kms_max = max(gather_floats(ring_kms if ring_kms is not None else 0.0))
+    if args.dump_outputs and rank == 0:  # before any later pass runs over the same batches
+        if not gpu:
+            raise SystemExit("bench: --dump-outputs needs the GPU path (no outputs under --selftest)")
+        dump_outputs(args.dump_outputs, headline, args.steps)
     # the same measurement at >= 50 steps (400 batches), in the same line: the K-step value is the
     # steady-state rate when the two agree
     steady = None
@@ -1839,7 +1886,7 @@ def run_rank(args) -> None:
 
     # ---- roofline: the headline launch timed alone; labelled variants beside (N = 1)
     roof, mroof, variants = None, None, {}
-    if gpu:
+    if gpu and args.full:
         launches = args.steps * BATCHES_PER_STEP
         roof = kernel_pass("in_place", launches, lag=False)
         mroof = multi_kernel("in_place", max(launches // MULTI_K, 10)) if headline == "multi" else None
@@ -2087,7 +2134,7 @@ def run_rank(args) -> None:
         if os.environ.get("NBG_BENCH_LAUNCHED") == "1":
             print(json.dumps(line), flush=True)  # the launcher adds PMC / e2e and prints the compact line
         else:
-            emit_line(line)  # a rank of torch.distributed.run: rank 0 prints the line itself
+            emit_line(line, record=args.full)  # a rank of torch.distributed.run: rank 0 prints the line itself
     if gpu:
         for m in mgs:
             m.close()
@@ -2131,7 +2178,18 @@ def parse_args(argv):
     ap.add_argument("--c4-batches", type=int, default=RING_BATCHES,
                     help="shards per rank in C4's device-resident pass (through the rank's ring)")
     ap.add_argument("--no-c4", action="store_true", help="skip the C4 block")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the steady-state pass, the roofline passes, every variant, the C4 "
+                         "block, the CPU baseline, the PMC traffic passes, the end-to-end pass and the full record "
+                         "file (each still switched off by its own --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path's last timed step computed to "
+                         "DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the K steps, print the line
+        args.steady_steps = 0
+        args.no_cpu_baseline = args.no_variants = args.no_c4 = args.no_pmc = args.no_e2e = True
+    return args
 
 
 def main():

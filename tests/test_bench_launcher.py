@@ -13,9 +13,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(n, tmp):
+def _run(n, tmp, *more):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--selftest",
-                        "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=300,
+                        "--steps", "3", "--warmup", "1", *more], capture_output=True, text=True, timeout=300,
                        env={**{k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")},
                             "NBG_BENCH_FULL": os.path.join(str(tmp), "full.json")})
     assert r.returncode == 0, r.stderr[-2000:]
@@ -27,7 +27,7 @@ def _run(n, tmp):
 
 @pytest.mark.parametrize("n", [1, 2, 4])
 def test_launcher_spawns_ranks(n, tmp_path):
-    line = _run(n, tmp_path)
+    line = _run(n, tmp_path, "--full")
     full = json.load(open(tmp_path / "full.json"))  # the full record beside the compact line
     assert full["n_gpus"] == n and len(full["lut_digest_per_rank"]) == n
     assert line["n_gpus"] == n
@@ -48,6 +48,19 @@ def test_launcher_spawns_ranks(n, tmp_path):
     else:
         assert "scatter_inclusive" not in c4
         assert "rccl_ranks" not in line
+
+
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the launcher prints the headline line and nothing beside it: no C4 block, no
+    variants, no roofline / PMC / end-to-end pass and no full record file."""
+    line = _run(1, tmp_path)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    for k in ("c4", "variants", "roofline", "steady_state", "e2e", "north_star", "full_record"):
+        assert k not in line, k
+    assert line["cpu_baseline"] is None
+    assert not (tmp_path / "full.json").exists()
 
 
 def test_rank_rejects_world_mismatch():

@@ -315,13 +315,13 @@ def test_oracle_is_test_infrastructure_only():
                 assert "maglev_ref" not in txt and "liborc" not in txt and "orc_" not in txt, f
 
 
-def test_host_operator_selftest():
+def test_host_operator_selftest(tmp_path):
     """C++ operator mirror pieces that need no GPU: MPSC ring semantics and the pcap port."""
     import subprocess
 
     exe = os.path.join(ROOT, "netbricks_amd", "host", "nb_host_selftest")
     if not os.path.exists(exe):
         subprocess.run(["make", "-C", os.path.dirname(exe)], check=True, capture_output=True)
-    r = subprocess.run([exe, os.path.join(GOLD, "http_lemmy.pcap"), "/tmp/nb_selftest_out.pcap"],
+    r = subprocess.run([exe, os.path.join(GOLD, "http_lemmy.pcap"), str(tmp_path / "nb_selftest_out.pcap")],
                        capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
