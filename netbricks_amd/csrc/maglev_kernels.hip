@@ -3373,9 +3373,13 @@ int launch_lpm_lookup(const uint16_t* tbl24, const uint16_t* tbl_long, const uin
   return NBG_OK;
 }
 
-int launch_hist(const HistArgs& a, void* stream) {
-  const size_t lds = static_cast<size_t>(a.nb + 1) * 4;
-  if (lds > 64 * 1024) {  // many backends: up to 32768 bins (128 KiB)
+namespace {
+
+// hist_kernel over hm.h[0 .. n): hm.per blocks per batch
+int launch_hist(const HistMulti& hm, uint32_t n, void* stream) {
+  const size_t lds = static_cast<size_t>(hm.h[0].nb + 1) * 4;
+  if (lds > 64 * 1024) {  // many backends: up to 32768 bins (128 KiB), one batch only
+    if (n > 1) return set_error(NBG_EINVAL, "hist (multi): at most 16383 bins");
     static bool attr = false;
     if (!attr) {
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3384,24 +3388,14 @@ int launch_hist(const HistArgs& a, void* stream) {
       attr = true;
     }
   }
-  HistMulti hm{};
-  hm.h[0] = a;
-  hm.per = a.n_parts;
-  hipLaunchKernelGGL(hist_kernel, dim3(a.n_parts), dim3(kGBlock), lds, static_cast<hipStream_t>(stream), hm);
+  hipLaunchKernelGGL(hist_kernel, dim3(hm.per * n), dim3(kGBlock), lds, static_cast<hipStream_t>(stream), hm);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(NBG_EIO, "hist launch: %s", hipGetErrorString(e));
+  if (e != hipSuccess)
+    return set_error(NBG_EIO, n == 1 ? "hist launch: %s" : "hist launch (multi): %s", hipGetErrorString(e));
   return NBG_OK;
 }
 
-int launch_hist_multi(const HistMulti& hm, uint32_t n, void* stream) {
-  if (n == 0 || n > kMaxMulti) return set_error(NBG_EINVAL, "hist (multi): %u batches", n);
-  if ((hm.h[0].nb + 1) * 4 > 64 * 1024) return set_error(NBG_EINVAL, "hist (multi): at most 16383 bins");
-  hipLaunchKernelGGL(hist_kernel, dim3(hm.per * n), dim3(kGBlock), (hm.h[0].nb + 1) * 4,
-                     static_cast<hipStream_t>(stream), hm);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(NBG_EIO, "hist launch (multi): %s", hipGetErrorString(e));
-  return NBG_OK;
-}
+}  // namespace
 
 __global__ __launch_bounds__(kBlock) void zero_kernel(uint32_t* p, uint32_t words) {
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < words; i += gridDim.x * kBlock) p[i] = 0;
@@ -3417,8 +3411,10 @@ int launch_zero(uint32_t* p, size_t words, void* stream) {
   return NBG_OK;
 }
 
-int launch_scan_multi(const ScanMulti& sm, uint32_t n, void* stream) {
-  if (n == 0 || n > kMaxMulti) return set_error(NBG_EINVAL, "scan (multi): %u batches", n);
+namespace {
+
+// scan_kernel over sm.s[0 .. n): blockIdx.y = batch
+int launch_scan(const ScanMulti& sm, uint32_t n, void* stream) {
   hipLaunchKernelGGL(scan_kernel, dim3((sm.s[0].nbins + kScanBins - 1) / kScanBins, n), dim3(kScanWaves * 64), 0,
                      static_cast<hipStream_t>(stream), sm);
   const hipError_t e = hipGetLastError();
@@ -3426,11 +3422,7 @@ int launch_scan_multi(const ScanMulti& sm, uint32_t n, void* stream) {
   return NBG_OK;
 }
 
-int launch_scan(const ScanArgs& a, void* stream) {
-  ScanMulti sm{};
-  sm.s[0] = a;
-  return launch_scan_multi(sm, 1, stream);
-}
+}  // namespace
 
 uint32_t classify_block_pkts() { return kBlock; }  // per tile per wave (64 packets x 4 waves)
 
@@ -3542,6 +3534,9 @@ int launch_host_ring(const HostRingArgs& r, uint32_t blocks, void* stream) {
   return NBG_OK;
 }
 
+namespace {
+
+// nb + 1 > kMaxGroupBins: two launches over one batch
 int launch_group_wide(const GroupArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(bin_base_kernel, dim3(1), dim3(kGBlock), 0, s, a);
@@ -3560,6 +3555,8 @@ int launch_group_wide(const GroupArgs& a, void* stream) {
   if (e != hipSuccess) return set_error(NBG_EIO, "group_wide launch: %s", hipGetErrorString(e));
   return NBG_OK;
 }
+
+}  // namespace
 
 // group_kernel: base[nbp] + tot[nbp] u32, cnt[waves][cst] u16, sslot[kChunk] u32 (40 KB at 1001 bins),
 // and <= 128 bins peer[waves][nbins + 1] u64 (22 KB at 66 bins);
@@ -3600,28 +3597,6 @@ bool group_compact(uint32_t nbins, bool ring_running) {
   return ring_running && group_lds(nbins, false) > group_lds_beside_ring();
 }
 
-// Default: sum the partition histograms from L2 inside the group kernel while the rows are
-// small (every block reads all of them), else a separate scan kernel.  NBG_GSCAN=0/2 forces a mode
-// (measurements).
-// Partition histograms from the classify kernel's per-block flush for few bins, from hist_kernel
-// for many (NBG_HIST_KERNEL_BINS overrides the threshold, for measurements).
-bool hist_in_classify(uint32_t nbins) {
-  static const uint32_t limit = [] {
-    const char* e = std::getenv("NBG_HIST_KERNEL_BINS");
-    return e ? static_cast<uint32_t>(std::atoi(e)) : 257u;
-  }();
-  return nbins < limit;
-}
-
-int pick_group_scan(uint32_t nbins, uint32_t n_parts) {
-  static const int forced = [] {
-    const char* e = std::getenv("NBG_GSCAN");
-    return e ? std::atoi(e) : -1;
-  }();
-  if (forced == kScanKernel || forced == kScanDirect) return forced;
-  return static_cast<size_t>(nbins) * n_parts <= 32u * 1024u ? kScanDirect : kScanKernel;
-}
-
 auto group_fn(uint32_t bits, int scan, bool compact) {
   if (compact)
     return bits <= 7 ? (scan == kScanDirect ? group_direct_kernel<kScanDirect, 7> : group_direct_kernel<kScanKernel, 7>)
@@ -3630,24 +3605,18 @@ auto group_fn(uint32_t bits, int scan, bool compact) {
                    : (scan == kScanDirect ? group_kernel<kScanDirect, 10> : group_kernel<kScanKernel, 10>);
 }
 
-int launch_group(const GroupArgs& a, int scan, void* stream, bool compact) {
-  GroupMulti gm{};
-  gm.g[0] = a;
-  gm.per = a.n_parts;
-  hipLaunchKernelGGL(group_fn(a.bits, scan, compact), dim3(a.n_parts), dim3(kGBlock), group_lds(a.nb + 1, compact),
-                     static_cast<hipStream_t>(stream), gm);
+int launch_group_plan(const GroupPlan& p, void* stream, bool compact) {
+  if (p.n == 0 || p.n > kMaxMulti || (p.wide && p.n != 1)) return set_error(NBG_EINVAL, "group (multi): %u batches", p.n);
+  int rc;
+  if (p.hist_kernel && (rc = launch_hist(p.hm, p.n, stream))) return rc;
+  if (p.scan == kScanKernel && (rc = launch_scan(p.sm, p.n, stream))) return rc;
+  if (p.wide) return launch_group_wide(p.gm.g[0], stream);
+  // one launch grouping gm.g[0 .. n): gm.per blocks per batch
+  hipLaunchKernelGGL(group_fn(p.bits, p.scan, compact), dim3(p.per * p.n), dim3(kGBlock), group_lds(p.nb + 1, compact),
+                     static_cast<hipStream_t>(stream), p.gm);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(NBG_EIO, "group launch: %s", hipGetErrorString(e));
-  return NBG_OK;
-}
-
-int launch_group_multi(const GroupMulti& gm, uint32_t n, int scan, void* stream, bool compact) {
-  const GroupArgs& a = gm.g[0];
-  if (n == 0 || n > kMaxMulti) return set_error(NBG_EINVAL, "group (multi): %u batches", n);
-  hipLaunchKernelGGL(group_fn(a.bits, scan, compact), dim3(gm.per * n), dim3(kGBlock), group_lds(a.nb + 1, compact),
-                     static_cast<hipStream_t>(stream), gm);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(NBG_EIO, "group launch (multi): %s", hipGetErrorString(e));
+  if (e != hipSuccess)
+    return set_error(NBG_EIO, p.n == 1 ? "group launch: %s" : "group launch (multi): %s", hipGetErrorString(e));
   return NBG_OK;
 }
 

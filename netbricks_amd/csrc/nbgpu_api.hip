@@ -58,6 +58,7 @@ struct nbg_maglev {
   int device = 0;
   uint32_t nb = 0;
   uint64_t m = 0;
+  uint64_t mu = 0;            // floor(2^64 / m) for Barrett (set with the LUT: upload)
   std::vector<uint16_t> lut_host;
   void* d_lut = nullptr;      // u8 (nb <= 256) or u16 entries, padded to 16 B
   bool wide = false;
@@ -75,23 +76,14 @@ struct nbg_maglev {
   uint32_t mparity = 0;
   uint32_t parity = 0;
   uint32_t* d_counts = nullptr;       // used when the caller passes no counts buffer
-  // deferred grouping (NBG_DEFER_GROUP): the group kernel's arguments, launched by finish_group
+  // deferred grouping (NBG_DEFER_GROUP): the launches of one or several batches' grouping, launched by
+  // finish_group
   bool pending = false;
-  int pending_scan_mode = 0;
-  bool pending_hist = false;
-  bool pending_wide = false;
-  HistArgs pending_hist_args{};
-  GroupArgs pending_args{};
-  ScanArgs pending_scan{};
-  uint32_t pending_multi = 0;         // > 0: the deferred group is a multi-batch group launch
-  GroupMulti pending_gm{};
-  bool pending_hist_multi = false;    // ... preceded by a multi-batch hist launch (many backends)
-  HistMulti pending_hm{};
-  ScanMulti pending_sm{};             // ... and a multi-batch scan launch (pending_scan_mode == kScanKernel)
+  GroupPlan pending_plan{};
   uint32_t* d_prefix_multi = nullptr; // [kMaxMulti][kMaxParts][nb+1] prefixes + [kMaxMulti][nb+1] totals (descriptor multi, scan kernel)
   // lagged grouping (NBG_GROUP_LAG): three rotating partition-histogram sets; a lagged classify
   // accumulates into set lag_idx, groups the pending batch from the previous set and zeroes the third
-  bool pending_lag = false;           // the pending group is a lagged one (pending_args / pending_lg)
+  bool pending_lag = false;           // the pending group is a lagged one (pending_plan, one batch / pending_lg)
   LagGroup pending_lg{};
   uint32_t* d_part_lag = nullptr;     // [3][kMaxParts][nb+1] (on first use)
   uint32_t lag_idx = 0;
@@ -358,6 +350,7 @@ void free_host_path(nbg_maglev* h) {
 int upload(nbg_maglev* h) {
   DeviceGuard g(h->device);
   h->wide = h->nb > 256;
+  h->mu = ~0ull / h->m + ((~0ull % h->m) + 1 == h->m ? 1 : 0);
   const size_t esz = h->wide ? 2 : 1;
   h->lut_bytes = static_cast<uint32_t>((h->m * esz + 15) & ~uint64_t(15));
   h->lut_alloc = (h->lut_bytes + 1023u) & ~1023u;
@@ -400,6 +393,28 @@ int upload(nbg_maglev* h) {
 // Many bins while a persistent ring runs on the device: the LDS-light group kernel, which co-runs
 // beside the ring instead of waiting for its end.
 bool compact_group(const nbg_maglev* h) { return group_compact(h->nb + 1, device_ring_running(h->device)); }
+
+// What a classify launch takes from the handle and the call's flags (a chained call comes without
+// NBG_SWAP_MACS: lpm's and maglev's swaps cancel); win_owned and lean are each site's own rule.
+void handle_args(const nbg_maglev* h, uint32_t flags, ClassifyArgs& a) {
+  a.lut = h->d_lut;
+  a.m = static_cast<uint32_t>(h->m);
+  a.mu = h->mu;
+  a.nb = h->nb;
+  a.swap = (flags & NBG_SWAP_MACS) ? 1u : 0u;
+  a.wb_full = (flags & NBG_WB_PARTIAL) ? 0u : 1u;
+}
+
+// The multi-batch calls' two ping-pong sets of partition rows, allocated (and zeroed) on first use.
+int ensure_multi_sets(nbg_maglev* h) {
+  if (h->d_part_multi) return NBG_OK;
+  const size_t set_words = static_cast<size_t>(kMaxMulti) * kMaxParts * (h->nb + 1);
+  NBG_HIP(hipMalloc(&h->d_part_multi, 2 * set_words * sizeof(uint32_t)));
+  SetupStream st;
+  (void)st.zero(h->d_part_multi, 2 * set_words * sizeof(uint32_t));
+  NBG_HIP(st.finish());
+  return NBG_OK;
+}
 
 bool use_lds_lut(const nbg_maglev* h, uint32_t flags) {
   return (flags & NBG_LUT_LDS) && h->lut_bytes <= 72 * 1024 && !device_ring_running(h->device);
@@ -640,14 +655,14 @@ int zero_captured(uint32_t* p, size_t words, void* stream) { return launch_zero(
 // standalone group kernel zeroes nothing there (the next lagged classify zeroes the sets).
 int flush_lag(nbg_maglev* h, hipStream_t s) {
   h->pending = h->pending_lag = false;
-  return launch_group(h->pending_args, kScanDirect, s, compact_group(h));
+  return launch_group_plan(h->pending_plan, s, compact_group(h));  // one batch, no hist, direct scan
 }
 
 // A lagged classify (NBG_GROUP_LAG): the streaming kernel accumulates this batch's partition rows
 // into lag set k, groups the pending batch (fuse) from set k - 1, and zeroes set k + 1 (mod 3) for
-// the call after next; this batch becomes the pending one.
-int classify_lag(nbg_maglev* h, ClassifyArgs& a, bool fuse, uint32_t n_parts, uint32_t part_pkts, uint32_t* d_perm,
-                 uint32_t* d_counts, hipStream_t s) {
+// the call after next; this batch becomes the pending one (gp: its plan, begun, no batch added yet).
+int classify_lag(nbg_maglev* h, ClassifyArgs& a, bool fuse, GroupPlan& gp, uint32_t* d_perm, uint32_t* d_counts,
+                 hipStream_t s) {
   const uint32_t nbins = h->nb + 1;
   const size_t set_words = static_cast<size_t>(kMaxParts) * nbins;
   if (!h->d_part_lag) {
@@ -671,31 +686,21 @@ int classify_lag(nbg_maglev* h, ClassifyArgs& a, bool fuse, uint32_t n_parts, ui
   h->pending = h->pending_lag = false;
   h->lag_dirty = (h->lag_dirty | (1u << k)) & ~(1u << z);
   h->lag_idx = z;
+  // its rows live in the lag set; a group launch of its own (flush_lag) zeroes nothing
+  plan_add(gp, a.backend, a.n_pkts, setk, nullptr, nullptr, d_perm, d_counts ? d_counts : h->d_counts);
+  plan_bin_base(gp, h->d_bin_base);
+  const GroupArgs& ga = gp.gm.g[0];
   LagGroup& p = h->pending_lg;
   p = LagGroup{};
-  p.backend = a.backend;
-  p.perm = d_perm;
-  p.counts = d_counts ? d_counts : h->d_counts;
-  p.part_hist = setk;
-  p.n_pkts = a.n_pkts;
-  p.part_pkts = part_pkts;
-  p.n_parts = n_parts;
-  p.hist16 = a.hist16;
-  GroupArgs& ga = h->pending_args;
-  ga = GroupArgs{};
-  ga.backend = a.backend;
-  ga.n_pkts = a.n_pkts;
-  ga.nb = h->nb;
-  uint32_t bits = 0;
-  while ((1u << bits) < nbins) ++bits;
-  ga.bits = bits;
-  ga.n_parts = n_parts;
-  ga.part_pkts = part_pkts;
-  ga.part_hist = setk;
-  ga.hist16 = a.hist16;
-  ga.counts = p.counts;
-  ga.perm = d_perm;
-  ga.bin_base = h->d_bin_base;
+  p.backend = ga.backend;
+  p.perm = ga.perm;
+  p.counts = ga.counts;
+  p.part_hist = ga.part_hist;
+  p.n_pkts = ga.n_pkts;
+  p.part_pkts = ga.part_pkts;
+  p.n_parts = ga.n_parts;
+  p.hist16 = ga.hist16;
+  h->pending_plan = gp;
   h->pending = h->pending_lag = true;
   return NBG_OK;
 }
@@ -730,7 +735,6 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
   const uint32_t nbins = h->nb + 1;
   if (group && nbins > kMaxWideBins)
     return set_error(NBG_EINVAL, "classify: group output supports at most %u backends", kMaxWideBins - 1);
-  const bool wide = group && nbins > kMaxGroupBins;  // wide grouping path (hist + scan + group_wide)
   // A call captured into a hipGraph is replayed with the same arguments, so it must not rely on the
   // ping-pong histograms (a replay would find them unzeroed): it zeroes and uses its own buffer,
   // and leaves the handle's parity alone.  Cross-stream ordering cannot be recorded during capture:
@@ -767,9 +771,9 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
     while (tpw < want && tpw < tpw_max) tpw <<= 1;
   }
   const int grid = static_cast<int>((n_tiles64 + uint64_t(tpw) * waves_per_block - 1) / (uint64_t(tpw) * waves_per_block));
-  const uint64_t per = (n_pkts + kChunk * kMaxParts - 1) / (kChunk * kMaxParts);
-  const uint32_t part_pkts = static_cast<uint32_t>(per * kChunk);
-  const uint32_t n_parts = static_cast<uint32_t>((n_pkts + part_pkts - 1) / part_pkts);
+  GroupPlan gp;  // also a call without grouping takes its partition size from it
+  plan_begin(gp, h->nb, n_pkts, kRowsClassify);
+  const uint32_t n_parts = gp.per;
   uint32_t* part_cur = capturing ? h->d_part_graph : h->d_part_hist + static_cast<size_t>(h->parity) * kMaxParts * nbins;
   uint32_t* part_next = capturing ? nullptr : h->d_part_hist + static_cast<size_t>(h->parity ^ 1u) * kMaxParts * nbins;
   const bool small = !lpm && use_small(n_pkts, nbins, flags, d_pkts);
@@ -802,28 +806,20 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
   a.fixed_len = fixed_len;
   a.n_pkts = static_cast<uint32_t>(n_pkts);
   a.tiles_per_wave = tpw;
-  a.lut = h->d_lut;
-  a.m = static_cast<uint32_t>(h->m);
+  handle_args(h, flags, a);
   a.lut_lds_bytes = lds ? h->lut_bytes : 0;
-  a.mu = ~0ull / h->m + ((~0ull % h->m) + 1 == h->m ? 1 : 0);  // floor(2^64 / m)
-  a.nb = h->nb;
-  a.swap = (flags & NBG_SWAP_MACS) && !lpm ? 1u : 0u;  // chain: lpm's and maglev's swaps cancel
   // a 64-B window per packet start is owned: fixed slots of >= 64 B, or the caller says so
   a.win_owned = (!d_off && stride >= 64) || (flags & NBG_OWNED_WINDOWS) ? 1u : 0u;
-  a.wb_full = (flags & NBG_WB_PARTIAL) ? 0u : 1u;
   a.lean = (!d_off && !d_len && a.win_owned && stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_pkts) & 15u) == 0 &&
             fixed_len >= 48)
                ? 1u
                : 0u;
   a.backend = d_backend;
   a.mac_out = d_mac_out;
-  const bool hist_k = group && !hist_in_classify(nbins);  // histograms by hist_kernel instead
+  const bool hist_k = group && gp.hist_kernel;  // histograms by hist_kernel instead
   a.part_hist = group && !hist_k ? part_cur : nullptr;
-  a.part_pkts = part_pkts;
-  const int scan = group && !wide ? pick_group_scan(nbins, n_parts) : kScanKernel;
-  // packed 16-bit partition rows where the classify kernel writes them and the group kernel sums
-  // them itself (partition counts stay below 65536)
-  a.hist16 = group && !hist_k && scan == kScanDirect && part_pkts < 65536 ? 1u : 0u;
+  a.part_pkts = gp.part_pkts;
+  a.hist16 = group ? gp.hist16 : 0u;
   if (lpm) {
     a.tbl24 = lpm->d_tbl24;
     a.tbl_long = lpm->d_tbl_long;
@@ -838,8 +834,8 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
   // NBG_GROUP_LAG: this batch's grouping is left pending (carried by the next call's launch) when
   // it takes the streaming kernel with in-kernel histograms and the direct scan; a pending lagged
   // group rides on this launch when both fit, else it is launched alone first
-  const bool lag = (flags & NBG_GROUP_LAG) && !capturing && group && !lpm && !wide && !hist_k &&
-                   scan == kScanDirect && a.lean && !lds && !(flags & NBG_LUT_TILED) && !small &&
+  const bool lag = (flags & NBG_GROUP_LAG) && !capturing && group && !lpm && !gp.wide && !hist_k &&
+                   gp.scan == kScanDirect && a.lean && !lds && !(flags & NBG_LUT_TILED) && !small &&
                    use_stream(h, n_pkts) && n_parts <= static_cast<uint32_t>(h->cus) &&
                    stream_lds(h->nb, !a.swap ? 0 : (a.mac_out ? 2 : 1), true) <= 160u * 1024u;
   const bool fuse = lag && h->pending_lag && h->pending_lg.n_parts <= static_cast<uint32_t>(h->cus);
@@ -890,7 +886,7 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
     a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
     if (capturing && a.part_hist)
       if ((rc = zero_captured(a.part_hist, static_cast<size_t>(n_parts) * nbins, stream))) return rc;
-    if (lag) return classify_lag(h, a, fuse, n_parts, part_pkts, d_perm, d_counts, static_cast<hipStream_t>(stream));
+    if (lag) return classify_lag(h, a, fuse, gp, d_perm, d_counts, static_cast<hipStream_t>(stream));
     rc = launch_classify_stream(a, stream_grid(h), stream);
   } else if (d_off && d_len && a.win_owned && !lds && (reinterpret_cast<uintptr_t>(d_pkts) & 15u) == 0 &&
              use_stream_desc(h, n_pkts, flags, lpm != nullptr, lpm || !a.swap ? 0 : (a.mac_out ? 2 : 1))) {
@@ -908,53 +904,35 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
     rc = launch_classify(a, h->wide, lds, grid, stream);
   }
   if (rc) return rc;
-  if (group) {
-    ScanArgs sa{};
-    sa.part_hist = part_cur;
-    sa.part_prefix = h->d_part_prefix;
-    sa.totals = h->d_totals;
-    sa.n_parts = n_parts;
-    sa.nbins = nbins;
-    HistArgs ha{};
-    ha.backend = d_backend;
-    ha.n_pkts = static_cast<uint32_t>(n_pkts);
-    ha.nb = h->nb;
-    ha.part_pkts = part_pkts;
-    ha.n_parts = n_parts;
-    ha.part_hist = part_cur;
-    GroupArgs ga{};
-    ga.backend = d_backend;
-    ga.n_pkts = static_cast<uint32_t>(n_pkts);
-    ga.nb = h->nb;
-    uint32_t bits = 0;
-    while ((1u << bits) < nbins) ++bits;
-    ga.bits = bits;
-    ga.n_parts = n_parts;
-    ga.part_pkts = part_pkts;
-    ga.part_hist = part_cur;
-    ga.part_prefix = h->d_part_prefix;
-    ga.totals = h->d_totals;
-    ga.hist16 = a.hist16;
-    ga.part_hist_next = part_next;
-    ga.next_words = part_next ? kMaxParts * nbins : 0u;
-    ga.counts = d_counts ? d_counts : h->d_counts;
-    ga.perm = d_perm;
-    ga.bin_base = h->d_bin_base;
-    if (!capturing) h->parity ^= 1u;
-    if (flags & NBG_DEFER_GROUP) {
-      h->pending = true;
-      h->pending_scan_mode = scan;
-      h->pending_hist = hist_k;
-      h->pending_hist_args = ha;
-      h->pending_args = ga;
-      h->pending_scan = sa;
-      h->pending_wide = wide;
-    } else {
-      if (hist_k && (rc = launch_hist(ha, stream))) return rc;
-      if (scan == kScanKernel && (rc = launch_scan(sa, stream))) return rc;
-      if ((rc = wide ? launch_group_wide(ga, stream) : launch_group(ga, scan, stream, compact_group(h)))) return rc;
-    }
+  if (!group) return NBG_OK;
+  plan_add(gp, d_backend, static_cast<uint32_t>(n_pkts), part_cur, h->d_part_prefix, h->d_totals, d_perm,
+           d_counts ? d_counts : h->d_counts);
+  plan_zero_next(gp, part_next, part_next ? kMaxParts * nbins : 0u);  // the other parity's set (none: captured)
+  plan_bin_base(gp, h->d_bin_base);
+  if (!capturing) h->parity ^= 1u;
+  if (flags & NBG_DEFER_GROUP) {
+    h->pending = true;
+    h->pending_plan = gp;
+    return NBG_OK;
   }
+  return launch_group_plan(gp, stream, compact_group(h));
+}
+
+// What the two multi-batch entry points check alike.  The handle's pending grouping: a lagged one is
+// launched alone first, a deferred one refuses the call.
+int multi_pending(nbg_maglev* h, const char* what, void* stream) {
+  if (h->pending_lag) {
+    const int rc = nbg_maglev_finish_group(h, stream);
+    if (rc) return rc;
+  }
+  if (h->pending) return set_error(NBG_EINVAL, "%s: a deferred group is pending (nbg_maglev_finish_group)", what);
+  return NBG_OK;
+}
+
+// Batch j: grouped like batch 0, and within the packet-count bound.
+int multi_batch_check(const char* what, uint32_t j, bool grouped, bool group, uint64_t n_pkts) {
+  if (grouped != group) return set_error(NBG_EINVAL, "%s: batch %u: every batch or none has perm/counts", what, j);
+  if (n_pkts >= (1ull << 30)) return set_error(NBG_EINVAL, "%s: batch %u: n_pkts must be < 2^30", what, j);
   return NBG_OK;
 }
 
@@ -973,18 +951,13 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
                      what);
   if (h->ring) return set_error(NBG_EBUSY, "%s: the handle's persistent ring is running", what);
   if (lpm && lpm->device != h->device) return set_error(NBG_EINVAL, "%s: lpm and maglev handles on different devices", what);
-  if (h->pending_lag) {  // a pending lagged group is launched alone first
-    const int rc = nbg_maglev_finish_group(h, stream);
-    if (rc) return rc;
-  }
-  if (h->pending) return set_error(NBG_EINVAL, "%s: a deferred group is pending (nbg_maglev_finish_group)", what);
+  int rc = multi_pending(h, what, stream);
+  if (rc) return rc;
   const bool group = batches[0].d_perm || batches[0].d_counts;
   uint64_t max_n = 0;
   for (uint32_t j = 0; j < n_batches; ++j) {
     const nbg_desc_batch& x = batches[j];
-    if ((x.d_perm || x.d_counts) != group)
-      return set_error(NBG_EINVAL, "%s: batch %u: every batch or none has perm/counts", what, j);
-    if (x.n_pkts >= (1ull << 30)) return set_error(NBG_EINVAL, "%s: batch %u: n_pkts must be < 2^30", what, j);
+    if ((rc = multi_batch_check(what, j, x.d_perm || x.d_counts, group, x.n_pkts))) return rc;
     if (x.n_pkts && (!x.d_pkts || !x.d_off || !x.d_len || !x.d_backend || (lpm && !x.d_gate)))
       return set_error(NBG_EINVAL, "%s: batch %u: null packet, offset, length, backend%s buffer", what, j,
                        lpm ? " or gate" : "");
@@ -997,9 +970,9 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
       return set_error(NBG_EINVAL, "%s: NBG_DEFER_GROUP needs at most %u backends", what, kMaxGroupBins - 1);
     for (uint32_t j = 0; j < n_batches; ++j) {
       const nbg_desc_batch& x = batches[j];
-      const int rc = classify_common(h, x.d_pkts, x.d_off, x.d_len, 0, 0, x.n_pkts, flags, x.d_backend, x.d_perm,
-                                     x.d_counts, nullptr, lpm, lpm_groups, x.d_gate, stream);
-      if (rc) return rc;
+      if ((rc = classify_common(h, x.d_pkts, x.d_off, x.d_len, 0, 0, x.n_pkts, flags, x.d_backend, x.d_perm,
+                                x.d_counts, nullptr, lpm, lpm_groups, x.d_gate, stream)))
+        return rc;
     }
     return NBG_OK;
   }
@@ -1008,38 +981,24 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
   NBG_HIP(hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cap));
   if (cap != hipStreamCaptureStatusNone) return set_error(NBG_EINVAL, "%s: cannot be captured in a graph", what);
   // one partition size for every batch (as the fixed-slot multi path): the group grid is
-  // n_batches x the largest batch's partitions
-  const uint64_t per = (max_n + kChunk * kMaxParts - 1) / (kChunk * kMaxParts);
-  const uint32_t part_pkts = static_cast<uint32_t>(std::max<uint64_t>(per, 1) * kChunk);
-  const uint32_t n_parts_max = static_cast<uint32_t>(std::max<uint64_t>((max_n + part_pkts - 1) / part_pkts, 1));
-  const bool hist_k = group && !hist_in_classify(nbins);
-  const int scan = group ? pick_group_scan(nbins, n_parts_max) : kScanDirect;
+  // n_batches x the largest batch's partitions.  Partition rows from the classify kernel's flush (few
+  // backends, rows accumulated: zeroed by the previous call's group launch) or from hist_kernel (many,
+  // rows stored whole)
+  GroupPlan gp;
+  plan_begin(gp, h->nb, max_n, kRowsClassify);
   const size_t set_words = static_cast<size_t>(kMaxMulti) * kMaxParts * nbins;
-  if (group && !h->d_part_multi) {
-    NBG_HIP(hipMalloc(&h->d_part_multi, 2 * set_words * sizeof(uint32_t)));
-    SetupStream st;
-    (void)st.zero(h->d_part_multi, 2 * set_words * sizeof(uint32_t));
-    NBG_HIP(st.finish());
-  }
-  if (group && scan == kScanKernel && !h->d_prefix_multi)
+  if (group && (rc = ensure_multi_sets(h))) return rc;
+  if (group && gp.scan == kScanKernel && !h->d_prefix_multi)
     NBG_HIP(hipMalloc(&h->d_prefix_multi, (set_words + static_cast<size_t>(kMaxMulti) * nbins) * sizeof(uint32_t)));
-  int rc = order_after_last(h, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  if ((rc = order_after_last(h, static_cast<hipStream_t>(stream)))) return rc;
   uint32_t* set_cur = group ? h->d_part_multi + static_cast<size_t>(h->mparity) * set_words : nullptr;
   uint32_t* set_next = group ? h->d_part_multi + static_cast<size_t>(h->mparity ^ 1u) * set_words : nullptr;
   ClassifyArgs a{};
   a.tiles_per_wave = std::min<uint32_t>(h->tiles_per_wave, 4u);  // NBG_TPW (measurement): 1, 2 or 4
-  a.lut = h->d_lut;
-  a.m = static_cast<uint32_t>(h->m);
-  a.mu = ~0ull / h->m + ((~0ull % h->m) + 1 == h->m ? 1 : 0);  // floor(2^64 / m)
-  a.nb = h->nb;
-  a.swap = (flags & NBG_SWAP_MACS) && !lpm ? 1u : 0u;  // chain: lpm's and maglev's swaps cancel
+  handle_args(h, flags, a);
   a.win_owned = (flags & NBG_OWNED_WINDOWS) ? 1u : 0u;
-  a.wb_full = (flags & NBG_WB_PARTIAL) ? 0u : 1u;
-  a.part_pkts = part_pkts;
-  // partition rows from the classify kernel's flush (few backends, rows accumulated: zeroed by the
-  // previous call's group launch) or from hist_kernel (many, rows stored whole)
-  a.hist16 = group && !hist_k && scan == kScanDirect && part_pkts < 65536 ? 1u : 0u;
+  a.part_pkts = gp.part_pkts;
+  a.hist16 = group ? gp.hist16 : 0u;
   if (lpm) {
     a.tbl24 = lpm->d_tbl24;
     a.tbl_long = lpm->d_tbl_long;
@@ -1047,64 +1006,30 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
   }
   const uint32_t bp = classify_block_pkts() * a.tiles_per_wave;
   DescBatches db{};
-  GroupMulti gm{};
-  HistMulti hm{};
-  ScanMulti sm{};
-  uint32_t bits = 0;
-  while ((1u << bits) < nbins) ++bits;
   uint32_t blocks = 0;
   for (uint32_t j = 0; j < n_batches; ++j) {
     const nbg_desc_batch& x = batches[j];
     const uint32_t n = static_cast<uint32_t>(x.n_pkts);
-    const uint32_t n_parts = n ? (n + part_pkts - 1) / part_pkts : 0u;
     uint32_t* rows = group ? set_cur + static_cast<size_t>(j) * kMaxParts * nbins : nullptr;
     db.pkts[j] = x.d_pkts;
     db.off[j] = x.d_off;
     db.len[j] = x.d_len;
     db.backend[j] = x.d_backend;
     db.gate[j] = x.d_gate;
-    db.part_hist[j] = group && !hist_k ? rows : nullptr;
+    db.part_hist[j] = group && !gp.hist_kernel ? rows : nullptr;
     db.n_pkts[j] = n;
     db.blk_base[j] = blocks;
     blocks += (n + bp - 1) / bp;
     if (!group) continue;
-    HistArgs& ha = hm.h[j];
-    ha.backend = x.d_backend;
-    ha.n_pkts = n;
-    ha.nb = h->nb;
-    ha.part_pkts = part_pkts;
-    ha.n_parts = n_parts;
-    ha.part_hist = rows;
     uint32_t* pre = h->d_prefix_multi ? h->d_prefix_multi + static_cast<size_t>(j) * kMaxParts * nbins : nullptr;
     uint32_t* tot = h->d_prefix_multi ? h->d_prefix_multi + set_words + static_cast<size_t>(j) * nbins : nullptr;
-    ScanArgs& sa = sm.s[j];
-    sa.part_hist = rows;
-    sa.part_prefix = pre;
-    sa.totals = tot;
-    sa.n_parts = std::max(n_parts, 1u);  // an empty batch scans row 0 (in bounds, unused: no group block)
-    sa.nbins = nbins;
-    GroupArgs& ga = gm.g[j];
-    ga.backend = x.d_backend;
-    ga.n_pkts = n;
-    ga.nb = h->nb;
-    ga.bits = bits;
-    ga.n_parts = n_parts;
-    ga.part_pkts = part_pkts;
-    ga.part_hist = rows;
-    ga.part_prefix = pre;
-    ga.totals = tot;
-    ga.hist16 = a.hist16;
-    // the next call's set is zeroed whenever a call on this handle may accumulate rows into it (the
-    // classify kernel's flush: few backends), even if this call's rows come from hist_kernel
-    ga.part_hist_next = hist_in_classify(nbins) ? set_next : nullptr;
-    ga.next_words = hist_in_classify(nbins) ? static_cast<uint32_t>(set_words) : 0u;
-    ga.counts = x.d_counts ? x.d_counts : h->d_counts;
-    ga.perm = x.d_perm;
+    plan_add(gp, x.d_backend, n, rows, pre, tot, x.d_perm, x.d_counts ? x.d_counts : h->d_counts);
   }
+  // the next call's set is zeroed whenever a call on this handle may accumulate rows into it (the
+  // classify kernel's flush: few backends), even if this call's rows come from hist_kernel
+  if (hist_in_classify(nbins)) plan_zero_next(gp, set_next, static_cast<uint32_t>(set_words));
   db.blk_base[n_batches] = blocks;
   db.n = n_batches;
-  hm.per = n_parts_max;
-  gm.per = n_parts_max;
   // what the batches share; per-batch pointers come from db (a's copies only select the layout)
   a.pkts = db.pkts[0];
   a.off = db.off[0];
@@ -1119,17 +1044,10 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
   h->mparity ^= 1u;
   if (flags & NBG_DEFER_GROUP) {
     h->pending = true;
-    h->pending_multi = n_batches;
-    h->pending_gm = gm;
-    h->pending_hist_multi = hist_k;
-    h->pending_hm = hm;
-    h->pending_sm = sm;
-    h->pending_scan_mode = scan;
+    h->pending_plan = gp;
     return NBG_OK;
   }
-  if (hist_k && (rc = launch_hist_multi(hm, n_batches, stream))) return rc;
-  if (scan == kScanKernel && (rc = launch_scan_multi(sm, n_batches, stream))) return rc;
-  return launch_group_multi(gm, n_batches, scan, stream, compact_group(h));
+  return launch_group_plan(gp, stream, compact_group(h));
 }
 
 }  // namespace
@@ -1163,19 +1081,14 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   if (flags & ~(NBG_SWAP_MACS | NBG_DEFER_GROUP))
     return set_error(NBG_EINVAL, "classify (multi): flags other than NBG_SWAP_MACS and NBG_DEFER_GROUP");
   if (h->ring) return set_error(NBG_EBUSY, "classify (multi): the handle's persistent ring is running");
-  if (h->pending_lag) {  // a pending lagged group is launched alone first
-    const int rc = nbg_maglev_finish_group(h, stream);
-    if (rc) return rc;
-  }
-  if (h->pending) return set_error(NBG_EINVAL, "classify (multi): a deferred group is pending (nbg_maglev_finish_group)");
+  int rc = multi_pending(h, "classify (multi)", stream);
+  if (rc) return rc;
   const bool group = batches[0].d_perm || batches[0].d_counts;
   uint64_t total = 0, max_n = 0;
   bool lean = stride >= 64 && stride % 16 == 0 && fixed_len >= 48 && stride < (1u << 24);
   for (uint32_t j = 0; j < n_batches; ++j) {
     const nbg_batch& x = batches[j];
-    if ((x.d_perm || x.d_counts) != group)
-      return set_error(NBG_EINVAL, "classify (multi): batch %u: every batch or none has perm/counts", j);
-    if (x.n_pkts >= (1ull << 30)) return set_error(NBG_EINVAL, "classify (multi): batch %u: n_pkts must be < 2^30", j);
+    if ((rc = multi_batch_check("classify (multi)", j, x.d_perm || x.d_counts, group, x.n_pkts))) return rc;
     if (x.n_pkts && (!x.d_pkts || !x.d_backend))
       return set_error(NBG_EINVAL, "classify (multi): batch %u: null packet or backend buffer", j);
     if ((x.d_mac_out != nullptr) != (batches[0].d_mac_out != nullptr))
@@ -1185,10 +1098,6 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
     max_n = std::max<uint64_t>(max_n, x.n_pkts);
   }
   const uint32_t nbins = h->nb + 1;
-  const uint64_t per = (max_n + kChunk * kMaxParts - 1) / (kChunk * kMaxParts);
-  const uint32_t part_pkts = static_cast<uint32_t>(std::max<uint64_t>(per, 1) * kChunk);
-  const uint32_t n_parts_max = static_cast<uint32_t>((max_n + part_pkts - 1) / part_pkts);
-  const int scan = group ? pick_group_scan(nbins, n_parts_max) : kScanDirect;
   // NBG_MULTI_HIST_KERNEL=1 (measurement): partition rows from one hist_kernel launch beside the group
   // launch instead of the classify kernel's per-unit flush (whose block barriers the ring kernel,
   // the faster in-place path, does not have)
@@ -1196,9 +1105,10 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
     const char* e = std::getenv("NBG_MULTI_HIST_KERNEL");
     return e && std::atoi(e) == 1;
   }();
-  const bool hist_k = group && multi_hist_k;
+  GroupPlan gp;
+  plan_begin(gp, h->nb, max_n, multi_hist_k ? kRowsHistKernel : kRowsClassify);
   const bool fused = lean && !h->wide && h->m <= 65537 && total >= 262144 && nbins <= 256 && use_stream(h, total) &&
-                     (!group || ((hist_k || hist_in_classify(nbins)) && scan != kScanKernel));
+                     (!group || ((multi_hist_k || hist_in_classify(nbins)) && gp.scan != kScanKernel));
   if (!fused && (flags & NBG_DEFER_GROUP)) {
     if (device_ring_running(h->device))
       return set_error(NBG_EINVAL, "classify (multi): NBG_DEFER_GROUP needs the streaming kernel, which cannot run while "
@@ -1210,9 +1120,9 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
     // one batch after another on the same stream (same results, one launch sequence each)
     for (uint32_t j = 0; j < n_batches; ++j) {
       const nbg_batch& x = batches[j];
-      const int rc = classify_common(h, x.d_pkts, nullptr, nullptr, stride, fixed_len, x.n_pkts, flags, x.d_backend,
-                                     x.d_perm, x.d_counts, x.d_mac_out, nullptr, 0, nullptr, stream);
-      if (rc) return rc;
+      if ((rc = classify_common(h, x.d_pkts, nullptr, nullptr, stride, fixed_len, x.n_pkts, flags, x.d_backend,
+                                x.d_perm, x.d_counts, x.d_mac_out, nullptr, 0, nullptr, stream)))
+        return rc;
     }
     return NBG_OK;
   }
@@ -1222,34 +1132,21 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   if (cap != hipStreamCaptureStatusNone)
     return set_error(NBG_EINVAL, "classify (multi): multi-launch batches cannot be captured in a graph");
   const size_t set_words = static_cast<size_t>(kMaxMulti) * kMaxParts * nbins;
-  if (group && !h->d_part_multi) {
-    NBG_HIP(hipMalloc(&h->d_part_multi, 2 * set_words * sizeof(uint32_t)));
-    SetupStream st;
-    (void)st.zero(h->d_part_multi, 2 * set_words * sizeof(uint32_t));
-    NBG_HIP(st.finish());
-  }
-  int rc = order_after_last(h, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  if (group && (rc = ensure_multi_sets(h))) return rc;
+  if ((rc = order_after_last(h, static_cast<hipStream_t>(stream)))) return rc;
   uint32_t* set_cur = group ? h->d_part_multi + static_cast<size_t>(h->mparity) * set_words : nullptr;
   uint32_t* set_next = group ? h->d_part_multi + static_cast<size_t>(h->mparity ^ 1u) * set_words : nullptr;
   ClassifyArgs a{};
   a.stride = stride;
   a.fixed_len = fixed_len;
-  a.lut = h->d_lut;
-  a.m = static_cast<uint32_t>(h->m);
-  a.mu = ~0ull / h->m + ((~0ull % h->m) + 1 == h->m ? 1 : 0);
-  a.nb = h->nb;
-  a.swap = (flags & NBG_SWAP_MACS) ? 1u : 0u;
+  handle_args(h, flags, a);
   a.win_owned = 1u;
-  a.wb_full = 1u;
   a.lean = 1u;
   a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
   a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
-  a.part_pkts = part_pkts;
-  a.hist16 = group && !hist_k && scan == kScanDirect && part_pkts < 65536 ? 1u : 0u;
+  a.part_pkts = gp.part_pkts;
+  a.hist16 = group ? gp.hist16 : 0u;
   StreamBatches sb{};
-  GroupMulti gm{};
-  HistMulti hm{};
   uint32_t units = 0;
   for (uint32_t j = 0; j < n_batches; ++j) {
     const nbg_batch& x = batches[j];
@@ -1257,36 +1154,16 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
     sb.backend[j] = x.d_backend;
     sb.mac_out[j] = x.d_mac_out;
     uint32_t* rows = group ? set_cur + static_cast<size_t>(j) * kMaxParts * nbins : nullptr;
-    sb.part_hist[j] = hist_k ? nullptr : rows;
+    sb.part_hist[j] = gp.hist_kernel ? nullptr : rows;
     sb.n_pkts[j] = static_cast<uint32_t>(x.n_pkts);
     sb.unit_base[j] = units;
     units += static_cast<uint32_t>((((x.n_pkts + 63) >> 6) + stream_waves_per_block() - 1) / stream_waves_per_block());
-    GroupArgs& ga = gm.g[j];
-    ga.backend = x.d_backend;
-    ga.n_pkts = static_cast<uint32_t>(x.n_pkts);
-    ga.nb = h->nb;
-    uint32_t bits = 0;
-    while ((1u << bits) < nbins) ++bits;
-    ga.bits = bits;
-    ga.n_parts = static_cast<uint32_t>((x.n_pkts + part_pkts - 1) / part_pkts);
-    ga.part_pkts = part_pkts;
-    ga.part_hist = rows;
-    ga.hist16 = a.hist16;
-    // zeroed for the next call even when this call's rows come from hist_kernel (stored whole): the
-    // next call may accumulate into them (the classify kernel's flush)
-    ga.part_hist_next = hist_in_classify(nbins) ? set_next : nullptr;
-    ga.next_words = hist_in_classify(nbins) ? static_cast<uint32_t>(set_words) : 0u;
-    ga.counts = x.d_counts ? x.d_counts : h->d_counts;
-    ga.perm = x.d_perm;
-    HistArgs& ha = hm.h[j];
-    ha.backend = x.d_backend;
-    ha.n_pkts = ga.n_pkts;
-    ha.nb = h->nb;
-    ha.part_pkts = part_pkts;
-    ha.n_parts = ga.n_parts;
-    ha.part_hist = rows;
+    if (group)  // the direct scan: no prefixes
+      plan_add(gp, x.d_backend, sb.n_pkts[j], rows, nullptr, nullptr, x.d_perm, x.d_counts ? x.d_counts : h->d_counts);
   }
-  hm.per = n_parts_max;
+  // zeroed for the next call even when this call's rows come from hist_kernel (stored whole): the
+  // next call may accumulate into them (the classify kernel's flush)
+  if (hist_in_classify(nbins)) plan_zero_next(gp, set_next, static_cast<uint32_t>(set_words));
   sb.unit_base[n_batches] = units;
   sb.n = n_batches;
   a.mac_out = sb.mac_out[0];  // selects the records mode; per-batch pointers come from sb
@@ -1297,22 +1174,14 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   h->last_stream = static_cast<hipStream_t>(stream);
   h->issued = true;
   if ((rc = launch_classify_stream_multi(a, sb, stream_grid(h), stream))) return rc;
-  if (group) {
-    h->mparity ^= 1u;
-    gm.per = n_parts_max;
-    if (flags & NBG_DEFER_GROUP) {
-      h->pending = true;
-      h->pending_multi = n_batches;
-      h->pending_gm = gm;
-      h->pending_hist_multi = hist_k;
-      h->pending_hm = hm;
-      h->pending_scan_mode = scan;
-      return NBG_OK;
-    }
-    if (hist_k && (rc = launch_hist_multi(hm, n_batches, stream))) return rc;
-    if ((rc = launch_group_multi(gm, n_batches, scan, stream, compact_group(h)))) return rc;
+  if (!group) return NBG_OK;
+  h->mparity ^= 1u;
+  if (flags & NBG_DEFER_GROUP) {
+    h->pending = true;
+    h->pending_plan = gp;
+    return NBG_OK;
   }
-  return NBG_OK;
+  return launch_group_plan(gp, stream, compact_group(h));
 }
 
 int nbg_chain_lpm_maglev_device(nbg_maglev* mg, nbg_lpm* lpm, uint32_t lpm_groups, uint8_t* d_pkts,
@@ -1383,22 +1252,7 @@ int nbg_maglev_finish_group(nbg_maglev* h, void* stream) {
   h->last_stream = static_cast<hipStream_t>(stream);
   if (h->pending_lag) return flush_lag(h, static_cast<hipStream_t>(stream));
   h->pending = false;
-  if (h->pending_multi) {
-    // fixed slots (nbg_maglev_classify_device_multi): partition rows from the classify kernel and the
-    // direct scan, one group launch; descriptor batches with many backends
-    // (nbg_maglev_classify_desc_multi) also a hist and a scan launch, each over all batches
-    const uint32_t n = h->pending_multi;
-    h->pending_multi = 0;
-    if (h->pending_hist_multi && (rc = launch_hist_multi(h->pending_hm, n, stream))) return rc;
-    if (h->pending_scan_mode == kScanKernel && (rc = launch_scan_multi(h->pending_sm, n, stream))) return rc;
-    return launch_group_multi(h->pending_gm, n, h->pending_scan_mode, stream, compact_group(h));
-  }
-  if (h->pending_hist && (rc = launch_hist(h->pending_hist_args, stream))) return rc;
-  if (h->pending_scan_mode == kScanKernel && (rc = launch_scan(h->pending_scan, stream))) return rc;
-  if ((rc = h->pending_wide ? launch_group_wide(h->pending_args, stream)
-                            : launch_group(h->pending_args, h->pending_scan_mode, stream, compact_group(h))))
-    return rc;
-  return NBG_OK;
+  return launch_group_plan(h->pending_plan, stream, compact_group(h));
 }
 
 int nbg_maglev_check(nbg_maglev* h) {
@@ -1755,44 +1609,10 @@ int ring_group_locked(nbg_ring* r, uint64_t ticket, uint32_t* d_perm, uint32_t* 
     if ((rc = launch_ring_gate(dcomp, dexit, static_cast<uint32_t>(ticket + 1), static_cast<uint32_t>(r->grid), s)))
       return rc;
   }
-  const uint64_t per = (n_pkts + kChunk * kMaxParts - 1) / (kChunk * kMaxParts);
-  const uint32_t part_pkts = static_cast<uint32_t>(per * kChunk);
-  const uint32_t n_parts = static_cast<uint32_t>((n_pkts + part_pkts - 1) / part_pkts);
-  HistArgs ha{};
-  ha.backend = backend;
-  ha.n_pkts = static_cast<uint32_t>(n_pkts);
-  ha.nb = r->nb;
-  ha.part_pkts = part_pkts;
-  ha.n_parts = n_parts;
-  ha.part_hist = gs->rows;
-  const int scan = pick_group_scan(nbins, n_parts);
-  ha.hist16 = scan == kScanDirect && part_pkts < 65536 ? 1u : 0u;  // packed rows for the direct prefix
-  if ((rc = launch_hist(ha, s))) return rc;
-  if (scan == kScanKernel) {
-    ScanArgs sa{};
-    sa.part_hist = gs->rows;
-    sa.part_prefix = gs->prefix;
-    sa.totals = gs->totals;
-    sa.n_parts = n_parts;
-    sa.nbins = nbins;
-    if ((rc = launch_scan(sa, s))) return rc;
-  }
-  GroupArgs ga{};
-  ga.backend = backend;
-  ga.n_pkts = static_cast<uint32_t>(n_pkts);
-  ga.nb = r->nb;
-  uint32_t bits = 0;
-  while ((1u << bits) < nbins) ++bits;
-  ga.bits = bits;
-  ga.n_parts = n_parts;
-  ga.part_pkts = part_pkts;
-  ga.part_hist = gs->rows;
-  ga.part_prefix = gs->prefix;
-  ga.totals = gs->totals;
-  ga.hist16 = ha.hist16;
-  ga.counts = d_counts;
-  ga.perm = d_perm;
-  return launch_group(ga, scan, s, group_compact(nbins, true));
+  GroupPlan gp;  // rows from hist_kernel, packed for the direct prefix
+  plan_begin(gp, r->nb, n_pkts, kRowsRing);
+  plan_add(gp, backend, static_cast<uint32_t>(n_pkts), gs->rows, gs->prefix, gs->totals, d_perm, d_counts);
+  return launch_group_plan(gp, s, group_compact(nbins, true));
 }
 
 // Batches first .. first + n - 1 grouped by one gate, one hist and one group launch on s (a
@@ -1818,11 +1638,9 @@ int ring_group_burst_locked(nbg_ring* r, uint64_t first, uint32_t n, uint32_t* c
     max_n = std::max(max_n, m);
     empty = empty || m == 0;
   }
-  const uint64_t per = (max_n + kChunk * kMaxParts - 1) / (kChunk * kMaxParts);
-  const uint32_t part_pkts = static_cast<uint32_t>(std::max<uint64_t>(per, 1) * kChunk);
-  const uint32_t n_parts_max = static_cast<uint32_t>((max_n + part_pkts - 1) / part_pkts);
-  const int scan = pick_group_scan(nbins, n_parts_max);
-  if (empty || scan == kScanKernel || n == 1) {
+  GroupPlan gp;
+  plan_begin(gp, r->nb, max_n, kRowsRing);
+  if (empty || gp.scan == kScanKernel || n == 1) {
     for (uint32_t j = 0; j < n; ++j) {
       const int rc = ring_group_locked(r, first + j, d_perm[j], d_counts[j], s);
       if (rc) return rc;
@@ -1840,37 +1658,12 @@ int ring_group_burst_locked(nbg_ring* r, uint64_t first, uint32_t n, uint32_t* c
     if ((rc = launch_ring_gate(dcomp, dexit, static_cast<uint32_t>(last + 1), static_cast<uint32_t>(r->grid), s)))
       return rc;
   }
-  HistMulti hm{};
-  GroupMulti gm{};
-  uint32_t bits = 0;
-  while ((1u << bits) < nbins) ++bits;
-  for (uint32_t j = 0; j < n; ++j) {
+  for (uint32_t j = 0; j < n; ++j) {  // the direct scan here: no prefixes
     const auto [backend, n_pkts] = r->rec[(first + j) & (r->slots - 1)];
     uint32_t* rows = gs->rows + static_cast<size_t>(j) * kMaxParts * nbins;
-    HistArgs& ha = hm.h[j];
-    ha.backend = backend;
-    ha.n_pkts = static_cast<uint32_t>(n_pkts);
-    ha.nb = r->nb;
-    ha.part_pkts = part_pkts;
-    ha.n_parts = static_cast<uint32_t>((n_pkts + part_pkts - 1) / part_pkts);
-    ha.part_hist = rows;
-    ha.hist16 = part_pkts < 65536 ? 1u : 0u;  // the direct prefix (scan == kScanDirect here)
-    GroupArgs& ga = gm.g[j];
-    ga.backend = backend;
-    ga.n_pkts = static_cast<uint32_t>(n_pkts);
-    ga.nb = r->nb;
-    ga.bits = bits;
-    ga.n_parts = ha.n_parts;
-    ga.part_pkts = part_pkts;
-    ga.part_hist = rows;
-    ga.hist16 = ha.hist16;
-    ga.counts = d_counts[j];
-    ga.perm = d_perm[j];
+    plan_add(gp, backend, static_cast<uint32_t>(n_pkts), rows, nullptr, nullptr, d_perm[j], d_counts[j]);
   }
-  hm.per = n_parts_max;
-  gm.per = n_parts_max;
-  if ((rc = launch_hist_multi(hm, n, s))) return rc;
-  return launch_group_multi(gm, n, scan, s, group_compact(nbins, true));
+  return launch_group_plan(gp, s, group_compact(nbins, true));
 }
 
 // Wait until `done()` holds, the ring has gone, or timeout_ms (0: none).  `done` runs under r->mu
@@ -1960,13 +1753,8 @@ int nbg_ring_start(nbg_maglev* h, uint32_t stride, uint16_t fixed_len, uint32_t 
   ClassifyArgs a{};
   a.stride = stride;
   a.fixed_len = fixed_len;
-  a.lut = h->d_lut;
-  a.m = static_cast<uint32_t>(h->m);
-  a.mu = ~0ull / h->m + ((~0ull % h->m) + 1 == h->m ? 1 : 0);  // floor(2^64 / m)
-  a.nb = h->nb;
-  a.swap = (flags & NBG_SWAP_MACS) ? 1u : 0u;
+  handle_args(h, flags, a);
   a.win_owned = 1;
-  a.wb_full = 1;
   a.lean = 1;
   a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
   a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
@@ -2391,13 +2179,8 @@ void small_args(const nbg_maglev* h, uint8_t* pkts, const uint32_t* off, const u
   a.stride = stride;
   a.n_pkts = static_cast<uint32_t>(n);
   a.tiles_per_wave = 1;
-  a.lut = h->d_lut;
-  a.m = static_cast<uint32_t>(h->m);
-  a.mu = ~0ull / h->m + ((~0ull % h->m) + 1 == h->m ? 1 : 0);  // floor(2^64 / m)
-  a.nb = h->nb;
-  a.swap = (flags & NBG_SWAP_MACS) ? 1u : 0u;
+  handle_args(h, flags, a);
   a.win_owned = (!off && stride >= 64) || (flags & NBG_OWNED_WINDOWS) ? 1u : 0u;
-  a.wb_full = (flags & NBG_WB_PARTIAL) ? 0u : 1u;
   a.win32 = win32 ? 1u : 0u;
   a.backend = backend;
   g = GroupArgs{};

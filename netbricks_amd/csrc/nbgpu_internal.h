@@ -237,6 +237,39 @@ struct GroupMulti {
 // summing the partition histograms straight from L2.
 enum GroupScan { kScanKernel = 0, kScanDirect = 2 };
 
+// Where a grouping's partition rows come from: the classify kernel's flush while the bin count
+// allows it (hist_in_classify; hist_kernel above), always hist_kernel (rows stored whole, 32-bit),
+// or always hist_kernel with rows packed for the direct prefix (the persistent ring's batches).
+enum RowsSource { kRowsClassify = 0, kRowsHistKernel = 1, kRowsRing = 2 };
+
+// Everything one grouping launch sequence (hist -> scan -> group) needs, for 1..kMaxMulti batches
+// that share one partition size.  Built by plan_begin + one plan_add per batch (group_plan.cpp: host
+// policy only, no HIP, no allocation), launched by launch_group_plan, or kept in the handle while
+// the grouping is deferred (NBG_DEFER_GROUP) or lagged (NBG_GROUP_LAG).
+struct GroupPlan {
+  HistMulti hm;
+  ScanMulti sm;
+  GroupMulti gm;
+  uint32_t n;          // batches added
+  uint32_t nb;
+  uint32_t part_pkts;  // packets per partition, a multiple of kChunk
+  uint32_t per;        // the grid's blocks per batch: the largest batch's partitions
+  uint32_t bits;       // ceil(log2(nb + 1))
+  int scan;            // kScanDirect / kScanKernel
+  bool hist_kernel;    // rows from hist_kernel (else the classify kernel wrote them)
+  bool wide;           // nb + 1 > kMaxGroupBins: group_wide (one batch only)
+  uint32_t hist16;     // ClassifyArgs::hist16 and GroupArgs::hist16 (HistArgs::hist16 with packed rows only)
+};
+// nb backends, the largest batch's packets, the rows' source: fixes everything but the batches
+void plan_begin(GroupPlan& p, uint32_t nb, uint64_t max_pkts, RowsSource src);
+// the next batch: hm.h[j], sm.s[j] and gm.g[j] (prefix / totals: scan_kernel's outputs, nullable
+// where the plan scans directly)
+void plan_add(GroupPlan& p, const uint16_t* backend, uint32_t n_pkts, uint32_t* rows, uint32_t* prefix,
+              uint32_t* totals, uint32_t* perm, uint32_t* counts);
+// the row set the group launch zeroes for the next call (every batch names the same one)
+void plan_zero_next(GroupPlan& p, uint32_t* part_hist_next, uint32_t next_words);
+void plan_bin_base(GroupPlan& p, uint32_t* bin_base);  // wide path: [nb + 1]
+
 // The host-batch server (nbg_host_ring_*): a persistent kernel whose blocks each take the next posted
 // small host batch (the direct path of nbg_maglev_host_submit) from a descriptor ring in pinned host
 // memory, so a batch costs no kernel launch.  Descriptors are written by producer threads: the
@@ -296,24 +329,20 @@ int stream_waves_per_block();
 // gathered from L2); stream_desc_lds: its dynamic LDS bytes (mode 0 read only, 1 in place, 2 records).
 int launch_classify_stream_desc(const ClassifyArgs& a, bool wide_lut, int grid, void* stream);
 size_t stream_desc_lds(uint32_t nb, int mode, bool wide_lut);
-int launch_scan(const ScanArgs& a, void* stream);
-int launch_scan_multi(const ScanMulti& sm, uint32_t n, void* stream);
 // the tile-per-wave classify kernel (256 threads, one 64-packet tile per wave) over db.n descriptor
 // batches; a carries what they share (LUT, flags, lpm tables), db what differs
 int launch_classify_desc_multi(const ClassifyArgs& a, const DescBatches& db, bool wide_lut, void* stream);
 uint32_t classify_block_pkts();  // packets per block and tile per wave of launch_classify_desc_multi
 int launch_zero(uint32_t* p, size_t words, void* stream);  // p[0, words) = 0 (one kernel)
-int launch_hist(const HistArgs& a, void* stream);
-int launch_hist_multi(const HistMulti& hm, uint32_t n, void* stream);  // nb + 1 <= 16384
-bool hist_in_classify(uint32_t nbins);
+bool hist_in_classify(uint32_t nbins);  // group_plan.cpp
 int launch_lpm_lookup(const uint16_t* tbl24, const uint16_t* tbl_long, const uint32_t* ips, uint64_t n,
                       uint16_t* gate, void* stream);
+// The plan's launches: hist (p.hist_kernel), scan (p.scan == kScanKernel), then group_wide (p.wide)
+// or one group launch over p.gm.g[0 .. p.n).  More than 16,383 bins (hist rows past 64 KiB of LDS)
+// and the wide path take one batch only.
 // compact: the LDS-light group kernel (group_compact(): many bins while a persistent ring runs)
-int launch_group(const GroupArgs& a, int scan, void* stream, bool compact);
-// one launch grouping gm.g[0 .. n): blocks per batch gm.per (the largest n_parts)
-int launch_group_multi(const GroupMulti& gm, uint32_t n, int scan, void* stream, bool compact);
+int launch_group_plan(const GroupPlan& p, void* stream, bool compact);
 bool group_compact(uint32_t nbins, bool ring_running);
-int launch_group_wide(const GroupArgs& a, void* stream);  // nb + 1 > kMaxGroupBins
 // One launch for a batch of at most small_max() packets and at most kMaxGroupBins bins: classify
 // and (when g.perm / g.counts) group.  The batch base must be 16-B aligned.
 // done (nullable): completion word the kernel sets to done_val once its outputs are visible to the host
@@ -324,7 +353,7 @@ int launch_classify_idx(const ClassifyArgs& a, int grid, void* stream);  // kIdx
 int launch_tiled_lookup(const TileArgs& a, void* stream);
 uint32_t lut_tiles(uint64_t m);
 size_t group_lds(uint32_t nbins, bool compact);
-int pick_group_scan(uint32_t nbins, uint32_t n_parts);
+int pick_group_scan(uint32_t nbins, uint32_t n_parts);  // group_plan.cpp
 int classify_grid(bool lds_lut, uint32_t lut_bytes, uint32_t nb, int device, int* grid);
 
 }  // namespace nbg

@@ -53,3 +53,43 @@ def test_compact_group_block_fits_beside_ring():
     assert lib.nbg_debug_group_lds(1001, 0) > budget  # C3 beside a ring: the compact kernel
     assert lib.nbg_debug_set_group_compact(2) != 0
     assert lib.nbg_debug_set_group_compact(-1) == 0
+
+
+_DIRECT, _KERNEL = 2, 0  # GroupScan (nbgpu_internal.h)
+
+# nb, rows' source (0 a handle's call, 1 the ring), n_pkts per batch ->
+# part_pkts, per, scan, hist_kernel, hist16, wide, n_parts per batch
+_GROUP_PLANS = [
+    (65, 0, [1048576], (4096, 256, _DIRECT, 0, 1, 0), [256]),
+    (65, 0, [1048577], (8192, 129, _DIRECT, 0, 1, 0), [129]),
+    (65, 0, [15728640], (61440, 256, _DIRECT, 0, 1, 0), [256]),
+    (65, 0, [16777216], (65536, 256, _DIRECT, 0, 0, 0), [256]),
+    (1000, 0, [131072], (4096, 32, _DIRECT, 1, 0, 0), [32]),
+    (1000, 0, [135168], (4096, 33, _KERNEL, 1, 0, 0), [33]),
+    (1000, 0, [1048576], (4096, 256, _KERNEL, 1, 0, 0), [256]),
+    (1500, 0, [140000], (4096, 35, _KERNEL, 1, 0, 1), [35]),
+    (65, 0, [262161, 0, 1, 5000, 70000], (4096, 65, _DIRECT, 0, 1, 0), [65, 0, 1, 2, 18]),
+    (65, 0, [0, 0], (4096, 1, _DIRECT, 0, 1, 0), [0, 0]),
+    (65, 1, [131072], (4096, 32, _DIRECT, 1, 1, 0), [32]),
+    (200, 1, [1048576], (4096, 256, _KERNEL, 1, 0, 0), [256]),
+]
+
+
+@pytest.mark.parametrize("nb,source,n_pkts,head,n_parts", _GROUP_PLANS)
+def test_group_plan_table(nb, source, n_pkts, head, n_parts):
+    """The grouping plan every launch site builds (group_plan.cpp), pinned for the edges of its rules:
+    partitions of whole 4096-packet chunks, at most 256 of them; packed 16-bit rows below 65536
+    packets per partition; the direct scan up to 32,768 row entries; hist_kernel from 257 bins (always
+    for the ring, whose rows are packed); the wide path above 1024 bins; one partition size for
+    several batches, an empty batch having no partition and a call of only empty ones a grid of one."""
+    import os
+
+    from netbricks_amd._lib import lib
+
+    if "NBG_GSCAN" in os.environ or "NBG_HIST_KERNEL_BINS" in os.environ:
+        pytest.skip("NBG_GSCAN / NBG_HIST_KERNEL_BINS override the plan's rules")
+    n = len(n_pkts)
+    out = (C.c_uint32 * (6 + n))()
+    assert lib.nbg_debug_group_plan(nb, (C.c_uint64 * n)(*n_pkts), n, source, out) == 0
+    assert tuple(out[:6]) == head
+    assert list(out[6:]) == n_parts

@@ -453,6 +453,44 @@ def test_defer_group_split(torch_cuda, mg65):
     _assert_same(got, exp)
 
 
+_DEFER_LUTS = {}
+
+
+@pytest.mark.parametrize("nb,m,n", [
+    (65, 65537, 140000),    # rows from the classify kernel's flush, direct scan
+    (1000, 655373, 140000), # hist_kernel + scan_kernel: 35 partitions x 1001 bins
+    (1000, 655373, 100000), # hist_kernel + direct scan: 25 partitions
+    (1500, 655373, 140000), # the wide path (hist + scan + bin_base + group_wide)
+])
+def test_defer_group_replay_paths(torch_cuda, nb, m, n):
+    """The deferred grouping's replay on another stream, for each launch sequence it can hold: fixed
+    64-B slots through the tile-per-wave kernel with NBG_DEFER_GROUP on one stream, then
+    nbg_maglev_finish_group on a second.  Two rounds on one handle: the second runs on the other
+    ping-pong row set, which the first round's deferred group launch zeroed."""
+    from netbricks_amd import Maglev, make_trace
+
+    torch = torch_cuda
+    names = [f"b{i}" for i in range(nb)]
+    if (nb, m) not in _DEFER_LUTS:
+        _DEFER_LUTS[(nb, m)] = orc.lut_build(names, m)
+    lut = _DEFER_LUTS[(nb, m)]
+    buf, _, _ = make_trace(n, 0, seed=nb + n)
+    _, exp_be, exp_perm, exp_cnt = _oracle(buf, n, lut, nb, stride=64, fixed_len=60)
+    mg = Maglev(names, m)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    for _ in range(2):
+        d = torch.from_numpy(buf.copy()).to("cuda:0")
+        torch.cuda.synchronize()
+        r = mg.group_by(d, n, defer_group=True, stream=s1.cuda_stream)
+        mg.finish_group(stream=s2.cuda_stream)
+        torch.cuda.synchronize()
+        mg.check()
+        np.testing.assert_array_equal(r.backend.view(torch.int16).cpu().numpy().view(np.uint16), exp_be)
+        np.testing.assert_array_equal(r.counts.view(torch.int32).cpu().numpy().view(np.uint32), exp_cnt)
+        np.testing.assert_array_equal(r.perm.view(torch.int32).cpu().numpy().view(np.uint32)[:n], exp_perm)
+    mg.close()
+
+
 def test_golden_packets_fixture(torch_cuda, mg65):
     """The committed golden vectors (tests/golden/packets.npz, made by the Python oracle)."""
     import os
