@@ -125,6 +125,10 @@ DEBUG_SIGNATURES = {
     "nbg_debug_group_lds": (C.c_uint64, [C.c_uint32, C.c_int]),
     "nbg_debug_lds_beside_ring": (C.c_uint64, []),
     "nbg_debug_group_plan": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    "nbg_debug_classify_route": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                           C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "nbg_debug_multi_fused": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.c_uint32]),
     "nbg_debug_hold_cus": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     "nbg_debug_host_win": (C.c_int, [_P, C.c_uint64]),
 }

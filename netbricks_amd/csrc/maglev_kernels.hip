@@ -3260,17 +3260,15 @@ size_t stream_desc_lds(uint32_t nb, int mode, bool wide_lut) {
   return (wide_lut ? 0u : kLutLds) + static_cast<size_t>(kStreamW) * wave + hwords * 4u;
 }
 
-int launch_classify_stream_desc(const ClassifyArgs& a, bool wide_lut, int grid, void* stream) {
-  const int mode = a.tbl24 || !a.swap ? 0 : (a.mac_out ? 2 : 1);
+int launch_classify_stream_desc(const ClassifyArgs& a, bool wide_lut, int mode, int grid, void* stream) {
   const size_t lds = stream_desc_lds(a.nb, mode, wide_lut);
   if (lds > 160u * 1024u) return set_error(NBG_EINVAL, "streaming classify (descriptors): %zu B of LDS", lds);
   hipStream_t s = static_cast<hipStream_t>(stream);
   return wide_lut ? launch_desc_lut<kGlobalU16>(a, mode, grid, lds, s) : launch_desc_lut<kLdsU8Tail>(a, mode, grid, lds, s);
 }
 
-int launch_classify_stream_multi(const ClassifyArgs& a, const StreamBatches& sb, int grid, void* stream) {
+int launch_classify_stream_multi(const ClassifyArgs& a, const StreamBatches& sb, int mode, int grid, void* stream) {
   const bool hist = a.part_hist != nullptr;
-  const int mode = !a.swap ? 0 : (a.mac_out ? 2 : 1);
   const size_t lds = stream_lds(a.nb, mode, false);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const LagGroup none{};
@@ -3281,11 +3279,8 @@ int launch_classify_stream_multi(const ClassifyArgs& a, const StreamBatches& sb,
               : launch_stream_mode<false, false, 0>(a, sb, none, mode, grid, lds, s);
 }
 
-int launch_classify_stream_lag(const ClassifyArgs& a, const LagGroup& lg, int grid, void* stream) {
-  const uint32_t nbins = a.nb + 1;
-  if (!a.part_hist || nbins > 512 || lg.n_parts > static_cast<uint32_t>(grid))
-    return set_error(NBG_EINVAL, "streaming classify (lagged group): %u bins, %u partitions on %d blocks", nbins,
-                     lg.n_parts, grid);
+// a's one batch as a StreamBatches
+static StreamBatches one_batch(const ClassifyArgs& a) {
   StreamBatches sb{};
   sb.pkts[0] = a.pkts;
   sb.backend[0] = a.backend;
@@ -3295,7 +3290,15 @@ int launch_classify_stream_lag(const ClassifyArgs& a, const LagGroup& lg, int gr
   sb.unit_base[0] = 0;
   sb.unit_base[1] = (((a.n_pkts + 63u) >> 6) + kStreamW - 1) / kStreamW;
   sb.n = 1;
-  const int mode = !a.swap ? 0 : (a.mac_out ? 2 : 1);
+  return sb;
+}
+
+int launch_classify_stream_lag(const ClassifyArgs& a, const LagGroup& lg, int mode, int grid, void* stream) {
+  const uint32_t nbins = a.nb + 1;
+  if (!a.part_hist || nbins > 512 || lg.n_parts > static_cast<uint32_t>(grid))
+    return set_error(NBG_EINVAL, "streaming classify (lagged group): %u bins, %u partitions on %d blocks", nbins,
+                     lg.n_parts, grid);
+  const StreamBatches sb = one_batch(a);
   const size_t lds = stream_lds(a.nb, mode, true);
   if (lds > 160u * 1024u) return set_error(NBG_EINVAL, "streaming classify (lagged group): %zu B of LDS", lds);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -3333,17 +3336,8 @@ int launch_ring_gate(const uint32_t* dcomp, const uint32_t* dexit, uint32_t targ
   return NBG_OK;
 }
 
-int launch_classify_stream(const ClassifyArgs& a, int grid, void* stream) {
-  StreamBatches sb{};
-  sb.pkts[0] = a.pkts;
-  sb.backend[0] = a.backend;
-  sb.mac_out[0] = a.mac_out;
-  sb.part_hist[0] = a.part_hist;
-  sb.n_pkts[0] = a.n_pkts;
-  sb.unit_base[0] = 0;
-  sb.unit_base[1] = (((a.n_pkts + 63u) >> 6) + kStreamW - 1) / kStreamW;
-  sb.n = 1;
-  return launch_classify_stream_multi(a, sb, grid, stream);
+int launch_classify_stream(const ClassifyArgs& a, int mode, int grid, void* stream) {
+  return launch_classify_stream_multi(a, one_batch(a), mode, grid, stream);
 }
 
 int launch_classify(const ClassifyArgs& a, bool wide_lut, bool lds_lut, int grid, void* stream) {

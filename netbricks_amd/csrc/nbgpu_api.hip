@@ -96,7 +96,7 @@ struct nbg_maglev {
   hipStream_t last_stream = nullptr;  // the stream of the handle's last launch
   bool issued = false;                // a launch has been issued on last_stream
   hipEvent_t order_ev = nullptr;      // cross-stream ordering of consecutive calls (order_after_last)
-  int grid_lds = 0, grid_global = 0;
+  int grid_lds = 0;                   // resident blocks of the LDS-LUT classify kernel
   uint32_t tiles_per_wave = 1;        // L2-LUT classify: 64-packet tiles per wave (NBG_TPW)
   // NBG_LUT_TILED scratch (grown on demand, outside graph capture): per-packet LUT indices, bucket
   // fill counts, and one bucket of (packet, index in tile) per 64-KiB LUT tile
@@ -212,10 +212,14 @@ std::vector<nbg_host_ring*> g_dev_hring;  // host-batch servers (nbg_host_ring_s
 // still query it after the stop (never a destroyed stream)
 std::vector<hipStream_t> g_hring_stream;
 
-bool device_ring_running(int device) {
+}  // namespace
+
+bool nbg::device_ring_running(int device) {
   std::lock_guard<std::mutex> g(g_dev_ring_mu);
   return device >= 0 && static_cast<size_t>(device) < g_dev_ring.size() && g_dev_ring[device] != nullptr;
 }
+
+namespace {
 
 struct DeviceGuard {
   int prev = -1;
@@ -252,15 +256,6 @@ struct SetupStream {
 // another stream, a host submit after device calls, or a caller that moves the handle between
 // streams): when the stream changes, the new stream waits for everything issued so far on the
 // previous one.  Calls that stay on one stream pay nothing.
-// Blocks of a streaming-classify launch: one per CU, or NBG_STREAM_GRID (measurement: 1..CUs).
-int stream_grid(const nbg_maglev* h) {
-  static const int forced = [] {
-    const char* e = std::getenv("NBG_STREAM_GRID");
-    return e ? std::atoi(e) : 0;
-  }();
-  return forced > 0 && forced <= h->cus ? forced : h->cus;
-}
-
 int order_after_last(nbg_maglev* h, hipStream_t s) {
   if (!h->issued || h->last_stream == s) return NBG_OK;
   if (!h->order_ev) NBG_HIP(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
@@ -380,29 +375,68 @@ int upload(nbg_maglev* h) {
   }
   if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->cus <= 0)
     return set_error(NBG_ENODEV, "hipDeviceGetAttribute(CU count) failed");
-  int rc = classify_grid(true, h->lut_bytes, h->nb, h->device, &h->grid_lds);
-  if (rc) return rc;
-  return classify_grid(false, 0, h->nb, h->device, &h->grid_global);
+  return classify_grid(true, h->lut_bytes, h->nb, h->device, &h->grid_lds);
 }
 
-// The LUT is gathered from L2 by default (measured faster: the LDS-staged copy costs
-// occupancy); NBG_LUT_LDS stages it in LDS when it fits.
-// While a persistent ring runs on the device, kernels that need a whole CU's LDS (the streaming
-// kernels, the LDS-staged LUT) would wait for it to end: batches of other handles then take the
-// tile-per-wave kernel, which co-runs in the LDS the ring leaves free.
 // Many bins while a persistent ring runs on the device: the LDS-light group kernel, which co-runs
 // beside the ring instead of waiting for its end.
 bool compact_group(const nbg_maglev* h) { return group_compact(h->nb + 1, device_ring_running(h->device)); }
 
-// What a classify launch takes from the handle and the call's flags (a chained call comes without
-// NBG_SWAP_MACS: lpm's and maglev's swaps cancel); win_owned and lean are each site's own rule.
-void handle_args(const nbg_maglev* h, uint32_t flags, ClassifyArgs& a) {
+// What pick_route (classify_route.cpp) reads of the handle.
+RouteFacts route_facts(const nbg_maglev* h) {
+  return {h->nb, h->m, h->lut_bytes, h->cus, h->grid_lds, h->tiles_per_wave, h->device, false};
+}
+
+// The ClassifyArgs of a call on its route, but for the grouping plan's fields (part_hist, part_pkts,
+// hist16).  The multi-batch sites and the ring come with what their batches share and a route of
+// their own kernel; per-batch pointers follow from their batch tables.
+void classify_args(const nbg_maglev* h, const ClassifyCall& c, const ClassifyRoute& r, ClassifyArgs& a) {
+  a = ClassifyArgs{};
+  a.pkts = c.pkts;
+  a.off = c.off;
+  a.len = r.fill_len ? h->d_fixed_len : c.len;
+  a.stride = c.stride;
+  a.fixed_len = c.fixed_len;
+  a.n_pkts = static_cast<uint32_t>(c.n_pkts);
+  a.tiles_per_wave = r.tpw;
   a.lut = h->d_lut;
   a.m = static_cast<uint32_t>(h->m);
   a.mu = h->mu;
   a.nb = h->nb;
-  a.swap = (flags & NBG_SWAP_MACS) ? 1u : 0u;
-  a.wb_full = (flags & NBG_WB_PARTIAL) ? 0u : 1u;
+  a.swap = (c.flags & NBG_SWAP_MACS) ? 1u : 0u;  // never with a chain: lpm's and maglev's swaps cancel
+  a.wb_full = (c.flags & NBG_WB_PARTIAL) ? 0u : 1u;
+  a.lut_lds_bytes = r.lds_lut ? h->lut_bytes : 0;
+  if (r.kernel == kKernelStream || (r.kernel == kKernelStreamDesc && !h->wide)) {
+    // the streaming kernels' u8 LUT: entries 0..65535 staged in LDS, entry 65536 of a 65537-slot table beside
+    a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
+    a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
+  }
+  a.win_owned = r.win_owned ? 1u : 0u;
+  a.lean = r.lean ? 1u : 0u;
+  a.backend = c.backend;
+  a.mac_out = c.lpm ? nullptr : c.mac_out;
+  if (c.lpm) {
+    a.tbl24 = c.lpm->d_tbl24;
+    a.tbl_long = c.lpm->d_tbl_long;
+    a.lpm_groups = c.lpm_groups;
+    a.gate = c.gate;
+  }
+  a.win32 = c.win32 ? 1u : 0u;
+  if (r.kernel == kKernelStreamDesc) a.sink = h->d_sink;
+}
+
+// What the batches of one streaming launch over lean slots share: the fused multi call, the ring.
+int lean_stream_args(const nbg_maglev* h, uint32_t stride, uint16_t fixed_len, uint32_t flags, bool records,
+                     ClassifyArgs& a) {
+  ClassifyCall c{};
+  c.stride = stride;
+  c.fixed_len = fixed_len;
+  c.flags = flags;
+  ClassifyRoute r{};
+  r.kernel = kKernelStream;
+  r.win_owned = r.lean = true;
+  classify_args(h, c, r, a);
+  return write_mode(flags, records, false);
 }
 
 // The multi-batch calls' two ping-pong sets of partition rows, allocated (and zeroed) on first use.
@@ -414,48 +448,6 @@ int ensure_multi_sets(nbg_maglev* h) {
   (void)st.zero(h->d_part_multi, 2 * set_words * sizeof(uint32_t));
   NBG_HIP(st.finish());
   return NBG_OK;
-}
-
-bool use_lds_lut(const nbg_maglev* h, uint32_t flags) {
-  return (flags & NBG_LUT_LDS) && h->lut_bytes <= 72 * 1024 && !device_ring_running(h->device);
-}
-
-// The streaming classify kernel serves fixed 64-B-aligned slots with a u8 LUT of at most 65537
-// entries (config C2); NBG_STREAM=0 selects the tile-per-wave kernel instead (A/B measurements).
-// Below ~2 units per block the per-block LUT staging (64 KiB from L2 for every CU) is not
-// amortised: smaller batches take the tile-per-wave kernel.
-bool use_stream(const nbg_maglev* h, uint64_t n_pkts) {
-  static const bool on = [] {
-    const char* e = std::getenv("NBG_STREAM");
-    return !e || std::atoi(e) != 0;
-  }();
-  return on && !h->wide && h->m <= 65537 && n_pkts >= 262144 && !device_ring_running(h->device);
-}
-
-// NBG_STREAM_DESC: descriptor layouts (IMIX offsets + lengths) with owned windows take the
-// streaming kernel too: the u8 LUT staged in LDS (read only, records, or the lpm chain), or the u16
-// LUT gathered from L2 (any mode, no chain).  The in-place mode with the u8 LUT does not fit LDS.
-// Opt-in: one stream, it classifies C5 in 27.1 us against 28.7 for the tile-per-wave kernel, but it
-// holds all LDS of every CU, so with three streams the tile-per-wave kernels co-running beat it
-// (profiles/r02_stream_desc_ab.txt).
-bool use_stream_desc(const nbg_maglev* h, uint64_t n_pkts, uint32_t flags, bool chain, int mode) {
-  if (!(flags & NBG_STREAM_DESC) || n_pkts < 262144 || device_ring_running(h->device)) return false;
-  if (h->wide) return !chain;
-  return h->m <= 65537 && mode != 1;
-}
-
-// Batches of at most 2048 packets take the single-launch small kernel (one block: 3.5 us per call
-// back to back at 32 packets and 6.9 us at 1024, against 9.5 and 10.6 us for classify + group; at
-// 4096 packets one CU is too little: 14.1 against 11.0 us, profiles/r02_small_batches.json).
-// NBG_SMALL=0 disables it (A/B measurements).
-bool use_small(uint64_t n_pkts, uint32_t nbins, uint32_t flags, const uint8_t* d_pkts) {
-  static const bool on = [] {
-    const char* e = std::getenv("NBG_SMALL");
-    return !e || std::atoi(e) != 0;
-  }();
-  return on && n_pkts <= std::min<uint32_t>(small_max(), 2048) && nbins <= kMaxGroupBins &&
-         !(flags & (NBG_DEFER_GROUP | NBG_LUT_LDS | NBG_LUT_TILED)) &&
-         (reinterpret_cast<uintptr_t>(d_pkts) & 15u) == 0;
 }
 
 // Persistent host worker pool for the host path's gather and MAC swap (bound by host
@@ -661,8 +653,8 @@ int flush_lag(nbg_maglev* h, hipStream_t s) {
 // A lagged classify (NBG_GROUP_LAG): the streaming kernel accumulates this batch's partition rows
 // into lag set k, groups the pending batch (fuse) from set k - 1, and zeroes set k + 1 (mod 3) for
 // the call after next; this batch becomes the pending one (gp: its plan, begun, no batch added yet).
-int classify_lag(nbg_maglev* h, ClassifyArgs& a, bool fuse, GroupPlan& gp, uint32_t* d_perm, uint32_t* d_counts,
-                 hipStream_t s) {
+int classify_lag(nbg_maglev* h, ClassifyArgs& a, int mode, bool fuse, GroupPlan& gp, uint32_t* d_perm,
+                 uint32_t* d_counts, hipStream_t s) {
   const uint32_t nbins = h->nb + 1;
   const size_t set_words = static_cast<size_t>(kMaxParts) * nbins;
   if (!h->d_part_lag) {
@@ -681,7 +673,7 @@ int classify_lag(nbg_maglev* h, ClassifyArgs& a, bool fuse, GroupPlan& gp, uint3
   LagGroup lg = fuse ? h->pending_lg : LagGroup{};
   lg.zero = h->d_part_lag + z * set_words;
   lg.zero_words = static_cast<uint32_t>(set_words);
-  const int rc = launch_classify_stream_lag(a, lg, h->cus, s);
+  const int rc = launch_classify_stream_lag(a, lg, mode, h->cus, s);
   if (rc) return rc;  // the pending group (if any) stays pending: finish_group or the next call launches it
   h->pending = h->pending_lag = false;
   h->lag_dirty = (h->lag_dirty | (1u << k)) & ~(1u << z);
@@ -705,44 +697,179 @@ int classify_lag(nbg_maglev* h, ClassifyArgs& a, bool fuse, GroupPlan& gp, uint3
   return NBG_OK;
 }
 
-// One classify (+ grouping) launch; `lpm` non-null runs the chained test/lpm stage first.
-// small_done (the host path's direct batches): the small kernel's completion word and value; the call
-// fails unless the batch takes the small kernel
-int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const uint16_t* d_len, uint32_t stride,
-                    uint16_t fixed_len, uint64_t n_pkts, uint32_t flags, uint16_t* d_backend, uint32_t* d_perm,
-                    uint32_t* d_counts, uint8_t* d_mac_out, const nbg_lpm* lpm, uint32_t lpm_groups,
-                    uint16_t* d_gate, void* stream, uint32_t* small_done = nullptr, uint32_t small_done_val = 0,
-                    bool win32 = false) {
+// Descriptor kernels read off[] and len[] both: offsets without lengths get a fixed_len-filled
+// array.  The small kernel reads fixed_len itself, so a captured call (always the small path)
+// never records this fill nor depends on the cached value (a captured fill, or a
+// capture relying on the cache, went stale when an eager call changed fixed_len).
+int grow_fixed_len(nbg_maglev* h, uint64_t n_pkts, uint16_t fixed_len, hipStream_t s) {
+  if (h->fixed_len_cap < n_pkts) {
+    (void)hipFree(h->d_fixed_len);
+    h->d_fixed_len = nullptr;
+    h->fixed_len_cap = 0;
+    NBG_HIP(hipMalloc(&h->d_fixed_len, n_pkts * sizeof(uint16_t)));
+    h->fixed_len_cap = n_pkts;
+    h->fixed_len_val = static_cast<uint16_t>(~fixed_len);  // force the fill below
+  }
+  if (h->fixed_len_val != fixed_len) {
+    NBG_HIP(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(h->d_fixed_len), fixed_len, h->fixed_len_cap, s));
+    h->fixed_len_val = fixed_len;
+  }
+  return NBG_OK;
+}
+
+// NBG_LUT_TILED: its scratch (grown on demand), the index kernel, then the per-tile lookup out of the
+// buckets
+int launch_tiled(nbg_maglev* h, ClassifyArgs& a, int grid, bool capturing, hipStream_t s) {
+  const uint32_t n_tiles = lut_tiles(h->m);
+  if (h->tiled_cap < a.n_pkts) {
+    if (capturing) return set_error(NBG_EINVAL, "classify: NBG_LUT_TILED scratch cannot grow in a graph");
+    (void)hipFree(h->d_idx);
+    (void)hipFree(h->d_cursor);
+    (void)hipFree(h->d_bucket);
+    h->d_idx = h->d_cursor = nullptr;
+    h->d_bucket = nullptr;
+    h->tiled_cap = 0;
+    NBG_HIP(hipMalloc(&h->d_idx, a.n_pkts * 4ull));
+    NBG_HIP(hipMalloc(&h->d_cursor, n_tiles * 4));
+    NBG_HIP(hipMalloc(&h->d_bucket, static_cast<size_t>(n_tiles) * a.n_pkts * 8));
+    h->tiled_cap = a.n_pkts;
+  }
+  a.idx_out = h->d_idx;
+  const int rc = launch_classify_idx(a, grid, s);
+  if (rc) return rc;
+  NBG_HIP(hipMemsetAsync(h->d_cursor, 0, n_tiles * 4, s));
+  TileArgs ta{};
+  ta.idx = h->d_idx;
+  ta.n_pkts = a.n_pkts;
+  ta.n_tiles = n_tiles;
+  ta.m = static_cast<uint32_t>(h->m);
+  ta.lut = h->d_lut;
+  ta.cursor = h->d_cursor;
+  ta.bucket = h->d_bucket;
+  ta.bucket_cap = static_cast<uint32_t>(h->tiled_cap);
+  ta.backend = a.backend;
+  return launch_tiled_lookup(ta, s);
+}
+
+// A call's ten common arguments, in the entry points' order; the rest (mac_out, the chain, the host
+// path's completion word) by field name.
+ClassifyCall device_call(uint8_t* pkts, const uint32_t* off, const uint16_t* len, uint32_t stride, uint16_t fixed_len,
+                         uint64_t n_pkts, uint32_t flags, uint16_t* backend, uint32_t* perm, uint32_t* counts) {
+  ClassifyCall c{};
+  c.pkts = pkts;
+  c.off = off;
+  c.len = len;
+  c.stride = stride;
+  c.fixed_len = fixed_len;
+  c.n_pkts = n_pkts;
+  c.flags = flags;
+  c.backend = backend;
+  c.perm = perm;
+  c.counts = counts;
+  return c;
+}
+
+// The small kernel's grouping outputs (counts into the handle's buffer when only perm is asked for)
+GroupArgs small_group(const nbg_maglev* h, const ClassifyCall& c) {
+  GroupArgs g{};
+  g.perm = c.perm;
+  g.counts = c.counts ? c.counts : (c.perm ? h->d_counts : nullptr);
+  return g;
+}
+
+// A validated call on its route r (gp: its plan, begun): grow the scratch the route needs, fill the
+// arguments, launch the route's kernel, then group, defer or lag.
+int classify_routed(nbg_maglev* h, const ClassifyCall& c, const ClassifyRoute& r, GroupPlan& gp, bool capturing,
+                    hipStream_t s) {
+  int rc = capturing ? NBG_OK : order_after_last(h, s);
+  if (rc) return rc;
+  if (r.fill_len && (rc = grow_fixed_len(h, c.n_pkts, c.fixed_len, s))) return rc;
+  // A captured call is replayed with the same arguments, so it must not rely on the ping-pong
+  // histograms (a replay would find them unzeroed): it zeroes and uses its own buffer, and leaves the
+  // handle's parity alone.
+  const bool group = c.perm || c.counts;
+  const uint32_t nbins = h->nb + 1;
+  const size_t set_words = static_cast<size_t>(kMaxParts) * nbins;
+  uint32_t* part_cur = capturing ? h->d_part_graph : h->d_part_hist + h->parity * set_words;
+  uint32_t* part_next = capturing ? nullptr : h->d_part_hist + (h->parity ^ 1u) * set_words;
+  ClassifyArgs a;
+  classify_args(h, c, r, a);
+  a.part_hist = group && !gp.hist_kernel ? part_cur : nullptr;  // else histograms by hist_kernel
+  a.part_pkts = gp.part_pkts;  // also a call without grouping takes its partition size from the plan
+  a.hist16 = group ? gp.hist16 : 0u;
+  if (!capturing) {
+    h->last_stream = s;
+    h->issued = true;
+  }
+  // a pending lagged group rides on this launch when this call lags too and it fits, else it is
+  // launched alone first
+  const bool fuse = r.lag && h->pending_lag && h->pending_lg.n_parts <= static_cast<uint32_t>(h->cus);
+  if (h->pending_lag && !fuse && (rc = flush_lag(h, s))) return rc;
+  if (c.done && r.kernel != kKernelSmall)
+    return set_error(NBG_EINVAL, "classify: a completion word needs the small kernel");
+  if (c.win32 && (r.kernel != kKernelSmall || a.swap))
+    return set_error(NBG_EINVAL, "classify: 32-B windows need the small kernel, no swap");
+  if (r.kernel == kKernelSmall) return launch_small(a, small_group(h, c), h->wide, s, c.done, c.done_val);
+  if (capturing && a.part_hist && r.kernel != kKernelTiled &&
+      (rc = zero_captured(a.part_hist, static_cast<size_t>(gp.per) * nbins, s)))
+    return rc;
+  switch (r.kernel) {
+    case kKernelTiled:
+      rc = launch_tiled(h, a, r.grid, capturing, s);
+      break;
+    case kKernelStream:
+      if (r.lag) return classify_lag(h, a, r.mode, fuse, gp, c.perm, c.counts, s);
+      rc = launch_classify_stream(a, r.mode, r.grid, s);
+      break;
+    case kKernelStreamDesc:
+      rc = launch_classify_stream_desc(a, h->wide, r.mode, r.grid, s);
+      break;
+    default:
+      rc = launch_classify(a, h->wide, r.lds_lut, r.grid, s);
+  }
+  if (rc) return rc;
+  if (!group) return NBG_OK;
+  plan_add(gp, c.backend, a.n_pkts, part_cur, h->d_part_prefix, h->d_totals, c.perm, c.counts ? c.counts : h->d_counts);
+  plan_zero_next(gp, part_next, part_next ? kMaxParts * nbins : 0u);  // the other parity's set (none: captured)
+  plan_bin_base(gp, h->d_bin_base);
+  if (!capturing) h->parity ^= 1u;
+  if (c.flags & NBG_DEFER_GROUP) {
+    h->pending = true;
+    h->pending_plan = gp;
+    return NBG_OK;
+  }
+  return launch_group_plan(gp, s, compact_group(h));
+}
+
+// One classify (+ grouping) call: validate, begin the plan, pick the route, run it.
+int classify_common(nbg_maglev* h, const ClassifyCall& c, void* stream) {
   if (!h) return set_error(NBG_EINVAL, "classify: null handle");
   if (h->ring) return set_error(NBG_EBUSY, "classify: the handle's persistent ring is running (nbg_ring_stop first)");
   if (h->pending && !h->pending_lag)
     return set_error(NBG_EINVAL, "classify: a deferred group is pending (nbg_maglev_finish_group)");
-  if ((flags & NBG_GROUP_LAG) && (flags & NBG_DEFER_GROUP))
+  if ((c.flags & NBG_GROUP_LAG) && (c.flags & NBG_DEFER_GROUP))
     return set_error(NBG_EINVAL, "classify: NBG_GROUP_LAG with NBG_DEFER_GROUP");
-  if (n_pkts >= (1ull << 30)) return set_error(NBG_EINVAL, "classify: n_pkts must be < 2^30");
-  if (n_pkts == 0) {
-    return d_counts ? zero_captured(d_counts, h->nb + 1, stream) : NBG_OK;  // a kernel: capturable
+  if (c.n_pkts >= (1ull << 30)) return set_error(NBG_EINVAL, "classify: n_pkts must be < 2^30");
+  if (c.n_pkts == 0) {
+    return c.counts ? zero_captured(c.counts, h->nb + 1, stream) : NBG_OK;  // a kernel: capturable
   }
-  if (!d_pkts || !d_backend) return set_error(NBG_EINVAL, "classify: null packet or backend buffer");
-  if (lpm && (!d_gate || lpm->device != h->device))
+  if (!c.pkts || !c.backend) return set_error(NBG_EINVAL, "classify: null packet or backend buffer");
+  if (c.lpm && (!c.gate || c.lpm->device != h->device))
     return set_error(NBG_EINVAL, "chain: null gate buffer, or lpm and maglev handles on different devices");
-  if (!d_off && stride == 0) return set_error(NBG_EINVAL, "classify: stride 0 without offsets");
-  if (!d_off && stride >= (1u << 24)) return set_error(NBG_EINVAL, "classify: stride must be < 2^24 (use offsets)");
-  if (!d_off && static_cast<unsigned __int128>(n_pkts) * stride > (1ull << 40))
+  if (!c.off && c.stride == 0) return set_error(NBG_EINVAL, "classify: stride 0 without offsets");
+  if (!c.off && c.stride >= (1u << 24)) return set_error(NBG_EINVAL, "classify: stride must be < 2^24 (use offsets)");
+  if (!c.off && static_cast<unsigned __int128>(c.n_pkts) * c.stride > (1ull << 40))
     return set_error(NBG_EINVAL, "classify: batch too large");
   DeviceGuard g(h->device);
-  const bool group = d_perm || d_counts;
-  const uint32_t nbins = h->nb + 1;
-  if (group && nbins > kMaxWideBins)
+  if ((c.perm || c.counts) && h->nb + 1 > kMaxWideBins)
     return set_error(NBG_EINVAL, "classify: group output supports at most %u backends", kMaxWideBins - 1);
-  // A call captured into a hipGraph is replayed with the same arguments, so it must not rely on the
-  // ping-pong histograms (a replay would find them unzeroed): it zeroes and uses its own buffer,
-  // and leaves the handle's parity alone.  Cross-stream ordering cannot be recorded during capture:
-  // the caller orders the capture after the handle's earlier work.
+  // Cross-stream ordering cannot be recorded during capture: the caller orders the capture after the
+  // handle's earlier work.
+  hipStream_t s = static_cast<hipStream_t>(stream);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  NBG_HIP(hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cap));
+  NBG_HIP(hipStreamIsCapturing(s, &cap));
   const bool capturing = cap != hipStreamCaptureStatusNone;
-  if (capturing && (flags & (NBG_DEFER_GROUP | NBG_GROUP_LAG)))
+  if (capturing && (c.flags & (NBG_DEFER_GROUP | NBG_GROUP_LAG)))
     return set_error(NBG_EINVAL, "classify: NBG_DEFER_GROUP / NBG_GROUP_LAG cannot be captured in a graph");
   if (capturing && h->pending)
     return set_error(NBG_EINVAL, "classify: a lagged group is pending (nbg_maglev_finish_group before capturing)");
@@ -750,173 +877,17 @@ int classify_common(nbg_maglev* h, uint8_t* d_pkts, const uint32_t* d_off, const
   // later eager call may reallocate: the NBG_LUT_TILED buckets and the fixed_len array that
   // descriptor batches without lengths get (grown on demand).  Everything else it touches is
   // allocated with the handle.
-  if (capturing && (flags & NBG_LUT_TILED))
+  if (capturing && (c.flags & NBG_LUT_TILED))
     return set_error(NBG_EINVAL, "classify: NBG_LUT_TILED cannot be captured in a graph (its scratch grows)");
-  if (capturing && d_off && !d_len && !(!lpm && use_small(n_pkts, nbins, flags, d_pkts)))
+  GroupPlan gp;
+  plan_begin(gp, h->nb, c.n_pkts, kRowsClassify);
+  const ClassifyRoute r = pick_route(route_facts(h), c, capturing, gp);
+  if (capturing && r.fill_len)
     return set_error(NBG_EINVAL, "classify: pass d_len to capture a descriptor batch of more than %u packets",
                      small_max());
-  int rc = capturing ? NBG_OK : order_after_last(h, static_cast<hipStream_t>(stream));
-  if (rc) return rc;
-  const bool lds = use_lds_lut(h, flags);
-  // each wave walks tpw consecutive 64-packet tiles (software-pipelined); the LDS-LUT variant
-  // runs a resident grid of 1024-thread blocks so that the LUT staging is amortised
-  const uint32_t waves_per_block = (lds ? kLdsBlock : kBlock) / 64;
-  const uint64_t n_tiles64 = (n_pkts + 63) / 64;
-  // a block's packets (64 * waves * tpw, a power of two <= kChunk) must not straddle a partition
-  const uint32_t tpw_max = kChunk / (64u * waves_per_block);
-  uint32_t tpw = std::min(h->tiles_per_wave, tpw_max);
-  if (lds) {
-    const uint64_t want = (n_tiles64 + uint64_t(h->grid_lds) * waves_per_block - 1) / (uint64_t(h->grid_lds) * waves_per_block);
-    tpw = 1;
-    while (tpw < want && tpw < tpw_max) tpw <<= 1;
-  }
-  const int grid = static_cast<int>((n_tiles64 + uint64_t(tpw) * waves_per_block - 1) / (uint64_t(tpw) * waves_per_block));
-  GroupPlan gp;  // also a call without grouping takes its partition size from it
-  plan_begin(gp, h->nb, n_pkts, kRowsClassify);
-  const uint32_t n_parts = gp.per;
-  uint32_t* part_cur = capturing ? h->d_part_graph : h->d_part_hist + static_cast<size_t>(h->parity) * kMaxParts * nbins;
-  uint32_t* part_next = capturing ? nullptr : h->d_part_hist + static_cast<size_t>(h->parity ^ 1u) * kMaxParts * nbins;
-  const bool small = !lpm && use_small(n_pkts, nbins, flags, d_pkts);
-
-  // Descriptor kernels read off[] and len[] both: offsets without lengths get a fixed_len-filled
-  // array.  The small kernel reads fixed_len itself, so a captured call (always the small path)
-  // never records this fill nor depends on the cached value (a captured fill, or a
-  // capture relying on the cache, went stale when an eager call changed fixed_len).
-  if (d_off && !d_len && !small) {
-    if (h->fixed_len_cap < n_pkts) {
-      (void)hipFree(h->d_fixed_len);
-      h->d_fixed_len = nullptr;
-      h->fixed_len_cap = 0;
-      NBG_HIP(hipMalloc(&h->d_fixed_len, n_pkts * sizeof(uint16_t)));
-      h->fixed_len_cap = n_pkts;
-      h->fixed_len_val = static_cast<uint16_t>(~fixed_len);  // force the fill below
-    }
-    if (h->fixed_len_val != fixed_len) {
-      NBG_HIP(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(h->d_fixed_len), fixed_len, h->fixed_len_cap,
-                                static_cast<hipStream_t>(stream)));
-      h->fixed_len_val = fixed_len;
-    }
-    d_len = h->d_fixed_len;
-  }
-  ClassifyArgs a{};
-  a.pkts = d_pkts;
-  a.off = d_off;
-  a.len = d_len;
-  a.stride = stride;
-  a.fixed_len = fixed_len;
-  a.n_pkts = static_cast<uint32_t>(n_pkts);
-  a.tiles_per_wave = tpw;
-  handle_args(h, flags, a);
-  a.lut_lds_bytes = lds ? h->lut_bytes : 0;
-  // a 64-B window per packet start is owned: fixed slots of >= 64 B, or the caller says so
-  a.win_owned = (!d_off && stride >= 64) || (flags & NBG_OWNED_WINDOWS) ? 1u : 0u;
-  a.lean = (!d_off && !d_len && a.win_owned && stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_pkts) & 15u) == 0 &&
-            fixed_len >= 48)
-               ? 1u
-               : 0u;
-  a.backend = d_backend;
-  a.mac_out = d_mac_out;
-  const bool hist_k = group && gp.hist_kernel;  // histograms by hist_kernel instead
-  a.part_hist = group && !hist_k ? part_cur : nullptr;
-  a.part_pkts = gp.part_pkts;
-  a.hist16 = group ? gp.hist16 : 0u;
-  if (lpm) {
-    a.tbl24 = lpm->d_tbl24;
-    a.tbl_long = lpm->d_tbl_long;
-    a.lpm_groups = lpm_groups;
-    a.gate = d_gate;
-    a.mac_out = nullptr;
-  }
-  if (!capturing) {
-    h->last_stream = static_cast<hipStream_t>(stream);
-    h->issued = true;
-  }
-  // NBG_GROUP_LAG: this batch's grouping is left pending (carried by the next call's launch) when
-  // it takes the streaming kernel with in-kernel histograms and the direct scan; a pending lagged
-  // group rides on this launch when both fit, else it is launched alone first
-  const bool lag = (flags & NBG_GROUP_LAG) && !capturing && group && !lpm && !gp.wide && !hist_k &&
-                   gp.scan == kScanDirect && a.lean && !lds && !(flags & NBG_LUT_TILED) && !small &&
-                   use_stream(h, n_pkts) && n_parts <= static_cast<uint32_t>(h->cus) &&
-                   stream_lds(h->nb, !a.swap ? 0 : (a.mac_out ? 2 : 1), true) <= 160u * 1024u;
-  const bool fuse = lag && h->pending_lag && h->pending_lg.n_parts <= static_cast<uint32_t>(h->cus);
-  if (h->pending_lag && !fuse && (rc = flush_lag(h, static_cast<hipStream_t>(stream)))) return rc;
-  if (small_done && !small) return set_error(NBG_EINVAL, "classify: a completion word needs the small kernel");
-  if (win32 && (!small || a.swap)) return set_error(NBG_EINVAL, "classify: 32-B windows need the small kernel, no swap");
-  a.win32 = win32 ? 1u : 0u;
-  if (small) {
-    GroupArgs g{};
-    g.perm = d_perm;
-    g.counts = d_counts ? d_counts : (d_perm ? h->d_counts : nullptr);
-    return launch_small(a, g, h->wide, stream, small_done, small_done_val);
-  }
-  const bool tiled = (flags & NBG_LUT_TILED) && h->wide && !lpm;
-  if (tiled) {
-    const uint32_t n_tiles = lut_tiles(h->m);
-    if (h->tiled_cap < n_pkts) {
-      if (capturing) return set_error(NBG_EINVAL, "classify: NBG_LUT_TILED scratch cannot grow in a graph");
-      (void)hipFree(h->d_idx);
-      (void)hipFree(h->d_cursor);
-      (void)hipFree(h->d_bucket);
-      h->d_idx = h->d_cursor = nullptr;
-      h->d_bucket = nullptr;
-      h->tiled_cap = 0;
-      NBG_HIP(hipMalloc(&h->d_idx, n_pkts * 4));
-      NBG_HIP(hipMalloc(&h->d_cursor, n_tiles * 4));
-      NBG_HIP(hipMalloc(&h->d_bucket, static_cast<size_t>(n_tiles) * n_pkts * 8));
-      h->tiled_cap = n_pkts;
-    }
-    a.idx_out = h->d_idx;
-    if ((rc = launch_classify_idx(a, grid, stream))) return rc;
-    NBG_HIP(hipMemsetAsync(h->d_cursor, 0, n_tiles * 4, static_cast<hipStream_t>(stream)));
-    TileArgs ta{};
-    ta.idx = h->d_idx;
-    ta.n_pkts = static_cast<uint32_t>(n_pkts);
-    ta.n_tiles = n_tiles;
-    ta.m = static_cast<uint32_t>(h->m);
-    ta.lut = h->d_lut;
-    ta.cursor = h->d_cursor;
-    ta.bucket = h->d_bucket;
-    ta.bucket_cap = static_cast<uint32_t>(h->tiled_cap);
-    ta.backend = d_backend;
-    rc = launch_tiled_lookup(ta, stream);
-  } else if (a.lean && !lds && !lpm && use_stream(h, n_pkts)) {
-    const uint64_t waves = static_cast<uint64_t>(h->cus) * stream_waves_per_block();
-    a.tiles_per_wave = static_cast<uint32_t>((n_tiles64 + waves - 1) / waves);
-    a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
-    a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
-    if (capturing && a.part_hist)
-      if ((rc = zero_captured(a.part_hist, static_cast<size_t>(n_parts) * nbins, stream))) return rc;
-    if (lag) return classify_lag(h, a, fuse, gp, d_perm, d_counts, static_cast<hipStream_t>(stream));
-    rc = launch_classify_stream(a, stream_grid(h), stream);
-  } else if (d_off && d_len && a.win_owned && !lds && (reinterpret_cast<uintptr_t>(d_pkts) & 15u) == 0 &&
-             use_stream_desc(h, n_pkts, flags, lpm != nullptr, lpm || !a.swap ? 0 : (a.mac_out ? 2 : 1))) {
-    if (!h->wide) {
-      a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
-      a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
-    }
-    if (capturing && a.part_hist)
-      if ((rc = zero_captured(a.part_hist, static_cast<size_t>(n_parts) * nbins, stream))) return rc;
-    a.sink = h->d_sink;
-    rc = launch_classify_stream_desc(a, h->wide, h->cus, stream);
-  } else {
-    if (capturing && a.part_hist)
-      if ((rc = zero_captured(a.part_hist, static_cast<size_t>(n_parts) * nbins, stream))) return rc;
-    rc = launch_classify(a, h->wide, lds, grid, stream);
-  }
-  if (rc) return rc;
-  if (!group) return NBG_OK;
-  plan_add(gp, d_backend, static_cast<uint32_t>(n_pkts), part_cur, h->d_part_prefix, h->d_totals, d_perm,
-           d_counts ? d_counts : h->d_counts);
-  plan_zero_next(gp, part_next, part_next ? kMaxParts * nbins : 0u);  // the other parity's set (none: captured)
-  plan_bin_base(gp, h->d_bin_base);
-  if (!capturing) h->parity ^= 1u;
-  if (flags & NBG_DEFER_GROUP) {
-    h->pending = true;
-    h->pending_plan = gp;
-    return NBG_OK;
-  }
-  return launch_group_plan(gp, stream, compact_group(h));
+  return classify_routed(h, c, r, gp, capturing, s);
 }
+
 
 // What the two multi-batch entry points check alike.  The handle's pending grouping: a lagged one is
 // launched alone first, a deferred one refuses the call.
@@ -970,9 +941,11 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
       return set_error(NBG_EINVAL, "%s: NBG_DEFER_GROUP needs at most %u backends", what, kMaxGroupBins - 1);
     for (uint32_t j = 0; j < n_batches; ++j) {
       const nbg_desc_batch& x = batches[j];
-      if ((rc = classify_common(h, x.d_pkts, x.d_off, x.d_len, 0, 0, x.n_pkts, flags, x.d_backend, x.d_perm,
-                                x.d_counts, nullptr, lpm, lpm_groups, x.d_gate, stream)))
-        return rc;
+      ClassifyCall c = device_call(x.d_pkts, x.d_off, x.d_len, 0, 0, x.n_pkts, flags, x.d_backend, x.d_perm, x.d_counts);
+      c.lpm = lpm;
+      c.lpm_groups = lpm_groups;
+      c.gate = x.d_gate;
+      if ((rc = classify_common(h, c, stream))) return rc;
     }
     return NBG_OK;
   }
@@ -993,17 +966,19 @@ int desc_multi_common(nbg_maglev* h, const nbg_desc_batch* batches, uint32_t n_b
   if ((rc = order_after_last(h, static_cast<hipStream_t>(stream)))) return rc;
   uint32_t* set_cur = group ? h->d_part_multi + static_cast<size_t>(h->mparity) * set_words : nullptr;
   uint32_t* set_next = group ? h->d_part_multi + static_cast<size_t>(h->mparity ^ 1u) * set_words : nullptr;
-  ClassifyArgs a{};
-  a.tiles_per_wave = std::min<uint32_t>(h->tiles_per_wave, 4u);  // NBG_TPW (measurement): 1, 2 or 4
-  handle_args(h, flags, a);
-  a.win_owned = (flags & NBG_OWNED_WINDOWS) ? 1u : 0u;
+  // what the batches share: the tile-per-wave kernel over descriptors
+  ClassifyCall c{};
+  c.flags = flags;
+  c.lpm = lpm;
+  c.lpm_groups = lpm_groups;
+  ClassifyRoute r{};
+  r.kernel = kKernelTileWave;
+  r.win_owned = flags & NBG_OWNED_WINDOWS;
+  r.tpw = std::min<uint32_t>(h->tiles_per_wave, 4u);  // NBG_TPW (measurement): 1, 2 or 4
+  ClassifyArgs a;
+  classify_args(h, c, r, a);
   a.part_pkts = gp.part_pkts;
   a.hist16 = group ? gp.hist16 : 0u;
-  if (lpm) {
-    a.tbl24 = lpm->d_tbl24;
-    a.tbl_long = lpm->d_tbl_long;
-    a.lpm_groups = lpm_groups;
-  }
   const uint32_t bp = classify_block_pkts() * a.tiles_per_wave;
   DescBatches db{};
   uint32_t blocks = 0;
@@ -1069,8 +1044,9 @@ int nbg_maglev_classify_device_ex(nbg_maglev* h, uint8_t* d_pkts, const uint32_t
                                   uint32_t stride, uint16_t fixed_len, uint64_t n_pkts, uint32_t flags,
                                   uint16_t* d_backend, uint32_t* d_perm, uint32_t* d_counts, uint8_t* d_mac_out,
                                   void* stream) {
-  return classify_common(h, d_pkts, d_off, d_len, stride, fixed_len, n_pkts, flags, d_backend, d_perm, d_counts,
-                         d_mac_out, nullptr, 0, nullptr, stream);
+  ClassifyCall c = device_call(d_pkts, d_off, d_len, stride, fixed_len, n_pkts, flags, d_backend, d_perm, d_counts);
+  c.mac_out = d_mac_out;
+  return classify_common(h, c, stream);
 }
 
 int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, uint32_t n_batches, uint32_t stride,
@@ -1084,8 +1060,7 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   int rc = multi_pending(h, "classify (multi)", stream);
   if (rc) return rc;
   const bool group = batches[0].d_perm || batches[0].d_counts;
-  uint64_t total = 0, max_n = 0;
-  bool lean = stride >= 64 && stride % 16 == 0 && fixed_len >= 48 && stride < (1u << 24);
+  uint64_t max_n = 0;
   for (uint32_t j = 0; j < n_batches; ++j) {
     const nbg_batch& x = batches[j];
     if ((rc = multi_batch_check("classify (multi)", j, x.d_perm || x.d_counts, group, x.n_pkts))) return rc;
@@ -1093,8 +1068,6 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
       return set_error(NBG_EINVAL, "classify (multi): batch %u: null packet or backend buffer", j);
     if ((x.d_mac_out != nullptr) != (batches[0].d_mac_out != nullptr))
       return set_error(NBG_EINVAL, "classify (multi): batch %u: every batch or none has d_mac_out", j);
-    if (x.n_pkts == 0 || (reinterpret_cast<uintptr_t>(x.d_pkts) & 15u)) lean = false;
-    total += x.n_pkts;
     max_n = std::max<uint64_t>(max_n, x.n_pkts);
   }
   const uint32_t nbins = h->nb + 1;
@@ -1107,8 +1080,7 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   }();
   GroupPlan gp;
   plan_begin(gp, h->nb, max_n, multi_hist_k ? kRowsHistKernel : kRowsClassify);
-  const bool fused = lean && !h->wide && h->m <= 65537 && total >= 262144 && nbins <= 256 && use_stream(h, total) &&
-                     (!group || ((multi_hist_k || hist_in_classify(nbins)) && gp.scan != kScanKernel));
+  const bool fused = multi_fused(route_facts(h), batches, n_batches, stride, fixed_len, group, multi_hist_k, gp);
   if (!fused && (flags & NBG_DEFER_GROUP)) {
     if (device_ring_running(h->device))
       return set_error(NBG_EINVAL, "classify (multi): NBG_DEFER_GROUP needs the streaming kernel, which cannot run while "
@@ -1120,8 +1092,8 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
     // one batch after another on the same stream (same results, one launch sequence each)
     for (uint32_t j = 0; j < n_batches; ++j) {
       const nbg_batch& x = batches[j];
-      if ((rc = classify_common(h, x.d_pkts, nullptr, nullptr, stride, fixed_len, x.n_pkts, flags, x.d_backend,
-                                x.d_perm, x.d_counts, x.d_mac_out, nullptr, 0, nullptr, stream)))
+      if ((rc = nbg_maglev_classify_device_ex(h, x.d_pkts, nullptr, nullptr, stride, fixed_len, x.n_pkts, flags,
+                                              x.d_backend, x.d_perm, x.d_counts, x.d_mac_out, stream)))
         return rc;
     }
     return NBG_OK;
@@ -1136,14 +1108,8 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   if ((rc = order_after_last(h, static_cast<hipStream_t>(stream)))) return rc;
   uint32_t* set_cur = group ? h->d_part_multi + static_cast<size_t>(h->mparity) * set_words : nullptr;
   uint32_t* set_next = group ? h->d_part_multi + static_cast<size_t>(h->mparity ^ 1u) * set_words : nullptr;
-  ClassifyArgs a{};
-  a.stride = stride;
-  a.fixed_len = fixed_len;
-  handle_args(h, flags, a);
-  a.win_owned = 1u;
-  a.lean = 1u;
-  a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
-  a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
+  ClassifyArgs a;
+  const int mode = lean_stream_args(h, stride, fixed_len, flags, batches[0].d_mac_out != nullptr, a);
   a.part_pkts = gp.part_pkts;
   a.hist16 = group ? gp.hist16 : 0u;
   StreamBatches sb{};
@@ -1173,7 +1139,7 @@ int nbg_maglev_classify_device_multi(nbg_maglev* h, const nbg_batch* batches, ui
   a.backend = sb.backend[0];
   h->last_stream = static_cast<hipStream_t>(stream);
   h->issued = true;
-  if ((rc = launch_classify_stream_multi(a, sb, stream_grid(h), stream))) return rc;
+  if ((rc = launch_classify_stream_multi(a, sb, mode, stream_grid(h->cus), stream))) return rc;
   if (!group) return NBG_OK;
   h->mparity ^= 1u;
   if (flags & NBG_DEFER_GROUP) {
@@ -1189,8 +1155,12 @@ int nbg_chain_lpm_maglev_device(nbg_maglev* mg, nbg_lpm* lpm, uint32_t lpm_group
                                 uint64_t n_pkts, uint32_t flags, uint16_t* d_gate, uint16_t* d_backend,
                                 uint32_t* d_perm, uint32_t* d_counts, void* stream) {
   if (!lpm) return set_error(NBG_EINVAL, "chain: null lpm handle");
-  return classify_common(mg, d_pkts, d_off, d_len, stride, fixed_len, n_pkts, flags & ~NBG_SWAP_MACS, d_backend,
-                         d_perm, d_counts, nullptr, lpm, lpm_groups, d_gate, stream);
+  ClassifyCall c = device_call(d_pkts, d_off, d_len, stride, fixed_len, n_pkts, flags & ~NBG_SWAP_MACS, d_backend,
+                               d_perm, d_counts);
+  c.lpm = lpm;
+  c.lpm_groups = lpm_groups;
+  c.gate = d_gate;
+  return classify_common(mg, c, stream);
 }
 
 int nbg_lpm_create(const uint32_t* prefixes, const uint8_t* lens, const uint16_t* gates, uint64_t n, int device,
@@ -1701,7 +1671,7 @@ int nbg_ring_start(nbg_maglev* h, uint32_t stride, uint16_t fixed_len, uint32_t 
   *out = nullptr;
   if (h->ring) return set_error(NBG_EBUSY, "ring_start: the handle already runs a ring");
   if (h->wide || h->m > 65537) return set_error(NBG_EINVAL, "ring_start: needs <= 255 backends and M <= 65537");
-  if (stride % 16 || stride < 64 || stride >= (1u << 24) || fixed_len < 48)
+  if (!lean_slots(stride >= 64, stride, fixed_len, nullptr) || stride >= (1u << 24))
     return set_error(NBG_EINVAL, "ring_start: fixed slots with stride %% 16 == 0, 64 <= stride < 2^24, fixed_len >= 48");
   if (flags & ~NBG_SWAP_MACS) return set_error(NBG_EINVAL, "ring_start: flags other than NBG_SWAP_MACS");
   if (h->pending) return set_error(NBG_EINVAL, "ring_start: a deferred or lagged group is pending");
@@ -1750,14 +1720,8 @@ int nbg_ring_start(nbg_maglev* h, uint32_t stride, uint16_t fixed_len, uint32_t 
     ring_free(r);
     return set_error(NBG_EIO, "ring_start: device address of the pinned ring");
   }
-  ClassifyArgs a{};
-  a.stride = stride;
-  a.fixed_len = fixed_len;
-  handle_args(h, flags, a);
-  a.win_owned = 1;
-  a.lean = 1;
-  a.lut_lds_bytes = std::min<uint32_t>(h->lut_alloc, 65536u);
-  a.lut_tail = h->m > 65536 ? h->lut_host[65536] : 0u;
+  ClassifyArgs a;  // pkts / n_pkts / backend come with each slot
+  const int mode = lean_stream_args(h, stride, fixed_len, flags, false, a);
   RingArgs ra{};
   ra.ctl = reinterpret_cast<RingCtl*>(hdev);
   ra.hdesc = reinterpret_cast<const RingDesc*>(hdev + sizeof(RingCtl));
@@ -1771,7 +1735,7 @@ int nbg_ring_start(nbg_maglev* h, uint32_t stride, uint16_t fixed_len, uint32_t 
   ra.grid = static_cast<uint32_t>(r->grid);
   ra.idle_ticks = static_cast<uint64_t>(r->idle_ms) * 100000u;  // 100 MHz
   (void)hipEventRecord(r->ev_start, r->stream);
-  if ((rc = launch_classify_ring(a, ra, a.swap ? 1 : 0, r->grid + 1, r->stream))) {
+  if ((rc = launch_classify_ring(a, ra, mode, r->grid + 1, r->stream))) {
     ring_free(r);
     return rc;
   }
@@ -2167,26 +2131,6 @@ int slot_complete(nbg_maglev* h, nbg_maglev::HostSlot& t) {
 }
 
 
-// The arguments the small kernel would be launched with for a host batch (classify_common's small
-// path): packets at pkts (+ off[i], or i * stride), lengths len[], outputs in pinned host memory.
-void small_args(const nbg_maglev* h, uint8_t* pkts, const uint32_t* off, const uint16_t* len, uint32_t stride,
-                uint64_t n, uint32_t flags, uint16_t* backend, uint32_t* perm, uint32_t* counts, ClassifyArgs& a,
-                GroupArgs& g, bool win32 = false) {
-  a = ClassifyArgs{};
-  a.pkts = pkts;
-  a.off = off;
-  a.len = len;
-  a.stride = stride;
-  a.n_pkts = static_cast<uint32_t>(n);
-  a.tiles_per_wave = 1;
-  handle_args(h, flags, a);
-  a.win_owned = (!off && stride >= 64) || (flags & NBG_OWNED_WINDOWS) ? 1u : 0u;
-  a.win32 = win32 ? 1u : 0u;
-  a.backend = backend;
-  g = GroupArgs{};
-  g.perm = perm;
-  g.counts = counts;
-}
 
 // Post a direct batch to the handle's host-batch server; false when the server has ended or stops
 // (the caller launches the small kernel instead).  Producer threads post concurrently: tickets come
@@ -2216,6 +2160,35 @@ bool host_ring_post(nbg_host_ring* r, const ClassifyArgs& a, const GroupArgs& g,
   __atomic_store_n(&d->seq, static_cast<uint32_t>(t + 1), __ATOMIC_RELEASE);
   __atomic_store_n(&r->ctl->posted, static_cast<uint32_t>(t + 1), __ATOMIC_RELEASE);
   return true;
+}
+
+// The plan and the route of a host batch; true when it is a direct one: the one small-kernel launch
+// (or the host-batch server) reads it out of pinned memory and stores its results there.
+bool host_route(const nbg_maglev* h, const ClassifyCall& c, GroupPlan& gp, ClassifyRoute& r) {
+  plan_begin(gp, h->nb, c.n_pkts, kRowsClassify);
+  r = pick_route(route_facts(h), c, false, gp);
+  return r.kernel == kKernelSmall;
+}
+
+// A direct batch of slot t, routed to the small kernel: post it to the handle's host-batch server, or
+// launch it; its completion is the word c.done.
+int submit_direct(nbg_maglev* h, nbg_maglev::HostSlot& t, const ClassifyCall& c, const ClassifyRoute& r,
+                  GroupPlan& gp) {
+  if (h->hring) {
+    classify_args(h, c, r, t.ra);  // kept: relaunched if the server ends first
+    t.rg = small_group(h, c);
+    t.on_ring = host_ring_post(h->hring, t.ra, t.rg, small_variant(h->wide, t.ra.m, h->nb, c.win32), c.done, c.done_val);
+  }
+  if (t.on_ring) {
+    t.watch = h->hring->stream;
+  } else {
+    const int rc = classify_routed(h, c, r, gp, false, h->host_compute);
+    if (rc) return rc;
+    t.watch = h->host_compute;
+  }
+  t.direct = true;
+  t.busy = true;
+  return NBG_OK;
 }
 
 }  // namespace
@@ -2274,36 +2247,22 @@ int nbg_maglev_host_submit(nbg_maglev* h, uint8_t* const* pkt_ptrs, const uint16
       hipStream_t hs = h->host_compute;
       const bool group = perm_out || counts_out;
       const uint32_t zflags = (flags & ~(NBG_DEFER_GROUP | NBG_GROUP_LAG)) | NBG_OWNED_WINDOWS | NBG_WB_PARTIAL;
-      if (use_small(n, h->nb + 1, zflags, reg.dev)) {
-        // direct: the one small-kernel launch (or the host-batch server) reads the offsets and lengths
-        // out of pinned memory and stores its results there (no copy on either side)
-        ClassifyArgs a;
-        GroupArgs ga;
-        small_args(h, reg.dev, reinterpret_cast<const uint32_t*>(t.dh_win), t.dh_len, 0, n, zflags, t.dh_backend,
-                   perm_out ? t.dh_perm : nullptr, group ? t.dh_counts : nullptr, a, ga);
-        t.on_ring = h->hring && host_ring_post(h->hring, a, ga, small_variant(h->wide, a.m, h->nb, false), t.dh_flag,
-                                               static_cast<uint32_t>(tk));
-        if (t.on_ring) {
-          t.watch = h->hring->stream;
-          t.ra = a;
-          t.rg = ga;
-        } else {
-          rc = classify_common(h, reg.dev, reinterpret_cast<const uint32_t*>(t.dh_win), t.dh_len, 0, 0, n, zflags,
-                               t.dh_backend, perm_out ? t.dh_perm : nullptr, group ? t.dh_counts : nullptr, nullptr,
-                               nullptr, 0, nullptr, hs, t.dh_flag, static_cast<uint32_t>(tk));
-          if (rc) return rc;
-          t.watch = hs;
-        }
-        t.direct = true;
-        t.busy = true;
+      // direct: the offsets and lengths are read out of pinned memory (no copy on either side)
+      ClassifyCall c = device_call(reg.dev, reinterpret_cast<const uint32_t*>(t.dh_win), t.dh_len, 0, 0, n, zflags,
+                                   t.dh_backend, perm_out ? t.dh_perm : nullptr, group ? t.dh_counts : nullptr);
+      c.done = t.dh_flag;
+      c.done_val = static_cast<uint32_t>(tk);
+      GroupPlan gp;
+      ClassifyRoute r;
+      if (host_route(h, c, gp, r)) {
+        if ((rc = submit_direct(h, t, c, r, gp))) return rc;
         *ticket = tk;
         return NBG_OK;
       }
       NBG_HIP(hipMemcpyAsync(t.d_win, h_off, n * 4, hipMemcpyHostToDevice, hs));
       NBG_HIP(hipMemcpyAsync(t.d_len, t.h_len, n * 2, hipMemcpyHostToDevice, hs));
-      rc = nbg_maglev_classify_device_ex(h, reg.dev, reinterpret_cast<const uint32_t*>(t.d_win), t.d_len, 0, 0, n,
-                                         (flags & ~(NBG_DEFER_GROUP | NBG_GROUP_LAG)) | NBG_OWNED_WINDOWS | NBG_WB_PARTIAL, t.d_backend,
-                                         perm_out ? t.d_perm : nullptr, group ? t.d_counts : nullptr, nullptr, hs);
+      rc = classify_common(h, device_call(reg.dev, reinterpret_cast<const uint32_t*>(t.d_win), t.d_len, 0, 0, n, zflags,
+                                          t.d_backend, perm_out ? t.d_perm : nullptr, group ? t.d_counts : nullptr), hs);
       if (rc) return rc;
       NBG_HIP(hipMemcpyAsync(t.h_backend, t.d_backend, n * 2, hipMemcpyDeviceToHost, hs));
       if (perm_out) NBG_HIP(hipMemcpyAsync(t.h_perm, t.d_perm, n * 4, hipMemcpyDeviceToHost, hs));
@@ -2319,7 +2278,15 @@ int nbg_maglev_host_submit(nbg_maglev* h, uint8_t* const* pkt_ptrs, const uint16
   // swapping) from byte 0 at the stride it needs
   const uint32_t sflags =
       (flags & ~(NBG_DEFER_GROUP | NBG_WB_PARTIAL | NBG_GROUP_LAG | NBG_SWAP_MACS)) | NBG_OWNED_WINDOWS;
-  const bool direct = use_small(n, h->nb + 1, sflags, t.dh_win);
+  hipStream_t hs = h->host_compute;
+  const bool group = perm_out || counts_out;
+  // the staged windows' stride is the gather's outcome (below); with lengths and owned windows no rule
+  // of the route reads it
+  ClassifyCall c = device_call(t.dh_win, nullptr, t.dh_len, 0, 0, n, sflags, t.dh_backend,
+                               perm_out ? t.dh_perm : nullptr, group ? t.dh_counts : nullptr);
+  GroupPlan gp;
+  ClassifyRoute r;
+  const bool direct = host_route(h, c, gp, r);
   // NBG_HOST_WIN48=1 (measurement): direct batches at 48-B windows, as before the 32-B staging
   static const bool win48 = [] {
     const char* e = std::getenv("NBG_HOST_WIN48");
@@ -2336,39 +2303,23 @@ int nbg_maglev_host_submit(nbg_maglev* h, uint8_t* const* pkt_ptrs, const uint16
   // and an event wait on the compute stream, kernels were seen reading windows whose H2D copy had
   // not landed (zero windows, sporadically, with many streams in the process).  The host gathers
   // the next batch while this one runs.
-  hipStream_t hs = h->host_compute;
-  const bool group = perm_out || counts_out;
   if (direct) {
     // direct: a batch of at most 2,048 packets (NetBricks' own bursts are 32) is classified and
     // grouped by one small-kernel launch that reads the staged windows out of pinned memory and
     // stores backend / perm / counts there.  The copies' fixed costs (a few us each on the DMA
     // engines, four to six per batch) were the whole cost of a small batch
-    ClassifyArgs a;
-    GroupArgs ga;
-    small_args(h, t.dh_win, nullptr, t.dh_len, win, n, sflags, t.dh_backend, perm_out ? t.dh_perm : nullptr,
-               group ? t.dh_counts : nullptr, a, ga, win == 32);
-    t.on_ring = h->hring && host_ring_post(h->hring, a, ga, small_variant(h->wide, a.m, h->nb, win == 32), t.dh_flag,
-                                           static_cast<uint32_t>(tk));
-    if (t.on_ring) {
-      t.watch = h->hring->stream;
-      t.ra = a;
-      t.rg = ga;
-    } else {
-      rc = classify_common(h, t.dh_win, nullptr, t.dh_len, win, 0, n, sflags, t.dh_backend,
-                           perm_out ? t.dh_perm : nullptr, group ? t.dh_counts : nullptr, nullptr, nullptr, 0, nullptr,
-                           hs, t.dh_flag, static_cast<uint32_t>(tk), win == 32);
-      if (rc) return rc;
-      t.watch = hs;
-    }
-    t.direct = true;
-    t.busy = true;
+    c.stride = win;
+    c.win32 = win == 32;
+    c.done = t.dh_flag;
+    c.done_val = static_cast<uint32_t>(tk);
+    if ((rc = submit_direct(h, t, c, r, gp))) return rc;
     *ticket = tk;
     return NBG_OK;
   }
   NBG_HIP(hipMemcpyAsync(t.d_win, t.h_win, n * win, hipMemcpyHostToDevice, hs));
   NBG_HIP(hipMemcpyAsync(t.d_len, t.h_len, n * 2, hipMemcpyHostToDevice, hs));
-  rc = nbg_maglev_classify_device_ex(h, t.d_win, nullptr, t.d_len, win, 0, n, sflags, t.d_backend,
-                                     perm_out ? t.d_perm : nullptr, group ? t.d_counts : nullptr, nullptr, hs);
+  rc = classify_common(h, device_call(t.d_win, nullptr, t.d_len, win, 0, n, sflags, t.d_backend,
+                                      perm_out ? t.d_perm : nullptr, group ? t.d_counts : nullptr), hs);
   if (rc) return rc;
   NBG_HIP(hipMemcpyAsync(t.h_backend, t.d_backend, n * 2, hipMemcpyDeviceToHost, hs));
   if (perm_out) NBG_HIP(hipMemcpyAsync(t.h_perm, t.d_perm, n * 4, hipMemcpyDeviceToHost, hs));

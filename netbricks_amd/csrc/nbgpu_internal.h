@@ -270,6 +270,70 @@ void plan_add(GroupPlan& p, const uint16_t* backend, uint32_t n_pkts, uint32_t* 
 void plan_zero_next(GroupPlan& p, uint32_t* part_hist_next, uint32_t next_words);
 void plan_bin_base(GroupPlan& p, uint32_t* bin_base);  // wide path: [nb + 1]
 
+// One classify (+ grouping) call as its entry point received it (nbgpu_api.hip classify_common).
+struct ClassifyCall {
+  uint8_t* pkts;
+  const uint32_t* off;    // nullable: fixed slots of `stride` bytes
+  const uint16_t* len;    // nullable: every packet fixed_len bytes
+  uint32_t stride;
+  uint16_t fixed_len;
+  uint64_t n_pkts;
+  uint32_t flags;
+  uint16_t* backend;
+  uint32_t* perm;         // nullable
+  uint32_t* counts;       // nullable
+  uint8_t* mac_out;       // nullable
+  const nbg_lpm* lpm;     // non-null: the chained test/lpm stage runs first
+  uint32_t lpm_groups;
+  uint16_t* gate;         // chain only
+  // the host path's direct batches: the small kernel's completion word and value, 32-B windows
+  uint32_t* done;
+  uint32_t done_val;
+  bool win32;
+};
+
+// What the route needs from the handle.  device < 0 (the diagnostics: no handle, no GPU): ring_forced
+// stands in for "a persistent ring runs on the device".
+struct RouteFacts {
+  uint32_t nb;
+  uint64_t m;
+  uint32_t lut_bytes;
+  int cus;
+  int grid_lds;             // resident blocks of the LDS-LUT classify kernel
+  uint32_t tiles_per_wave;  // NBG_TPW
+  int device;
+  bool ring_forced;
+};
+
+enum ClassifyKernel { kKernelSmall = 0, kKernelTiled = 1, kKernelStream = 2, kKernelStreamDesc = 3, kKernelTileWave = 4 };
+
+// The classify half of a call's policy (classify_route.cpp: host only, no HIP, no allocation): the
+// kernel, its LUT source, layout rules, write mode and geometry.  It travels beside ClassifyArgs.
+struct ClassifyRoute {
+  ClassifyKernel kernel;
+  bool lds_lut;     // NBG_LUT_LDS honoured: the tile-per-wave kernel stages the LUT in LDS
+  bool win_owned;   // every packet start owns a 64-B window
+  bool lean;        // lean_slots() holds for a fixed-slot batch without len[]
+  bool fill_len;    // offsets without lengths: the kernel reads a fixed_len-filled len[]
+  bool lag;         // NBG_GROUP_LAG: the grouping rides on the next call's streaming launch
+  int mode;         // what the kernel writes: 0 read only, 1 MAC swap in place, 2 12-B records
+  uint32_t tpw;     // ClassifyArgs::tiles_per_wave for the kernel taken
+  int grid;
+};
+// the fixed-slot rule of the lean kernels: owned 64-B windows at 16-B aligned starts, headers within
+// fixed_len >= 48 bytes (base: the batch's first slot; null where the batches come later)
+bool lean_slots(bool owned, uint32_t stride, uint32_t fixed_len, const void* base);
+// ClassifyRoute::mode of a call with NBG_SWAP_MACS or not, 12-B records (mac_out) or not, chained or not
+int write_mode(uint32_t flags, bool records, bool chain);
+// gp: the call's plan, begun (the lag rule reads how it will be grouped)
+ClassifyRoute pick_route(const RouteFacts& f, const ClassifyCall& c, bool capturing, const GroupPlan& gp);
+// nbg_maglev_classify_device_multi: all batches through one streaming launch and one grouping
+// (gp: begun for the largest batch; rows_forced: its rows come from hist_kernel by request)
+bool multi_fused(const RouteFacts& f, const nbg_batch* batches, uint32_t n_batches, uint32_t stride,
+                 uint32_t fixed_len, bool group, bool rows_forced, const GroupPlan& gp);
+int stream_grid(int cus);            // blocks of a streaming-classify launch
+bool device_ring_running(int device);  // nbgpu_api.hip: a persistent ring holds the device's LDS
+
 // The host-batch server (nbg_host_ring_*): a persistent kernel whose blocks each take the next posted
 // small host batch (the direct path of nbg_maglev_host_submit) from a descriptor ring in pinned host
 // memory, so a batch costs no kernel launch.  Descriptors are written by producer threads: the
@@ -308,13 +372,14 @@ uint32_t small_variant(bool wide_lut, uint32_t m, uint32_t nb, bool win32);
 // Launchers (maglev_kernels.hip).  `wide_lut` = u16 entries; `lds_lut` = stage in LDS.
 int launch_classify(const ClassifyArgs& a, bool wide_lut, bool lds_lut, int grid, void* stream);
 // Streaming classify (lean fixed slots, u8 LUT of <= 65537 entries staged in LDS): one block per
-// CU; a.tiles_per_wave = the contiguous 64-packet tiles of each of the grid's waves.
-int launch_classify_stream(const ClassifyArgs& a, int grid, void* stream);
+// CU; a.tiles_per_wave = the contiguous 64-packet tiles of each of the grid's waves; mode: the
+// route's (0 read only, 1 in place, 2 records).
+int launch_classify_stream(const ClassifyArgs& a, int mode, int grid, void* stream);
 // The same over several batches (sb.n >= 1; a carries what they share)
-int launch_classify_stream_multi(const ClassifyArgs& a, const StreamBatches& sb, int grid, void* stream);
+int launch_classify_stream_multi(const ClassifyArgs& a, const StreamBatches& sb, int mode, int grid, void* stream);
 // One batch (a.part_hist set) plus the grouping of the pending batch lg (NBG_GROUP_LAG); needs
 // lg.n_parts <= grid and (nb + 1) * lg.n_parts within the direct-scan limit (pick_group_scan)
-int launch_classify_stream_lag(const ClassifyArgs& a, const LagGroup& lg, int grid, void* stream);
+int launch_classify_stream_lag(const ClassifyArgs& a, const LagGroup& lg, int mode, int grid, void* stream);
 size_t stream_lds(uint32_t nb, int mode, bool lag);
 // The persistent ring kernel (nbg_ring_start): a.pkts / n_pkts / backend come from the ring; mode 0
 // read only, 1 MAC swap in place.  Returns after the launch; the kernel runs until stop or idle.
@@ -327,7 +392,7 @@ int launch_ring_gate(const uint32_t* dcomp, const uint32_t* dexit, uint32_t targ
 int stream_waves_per_block();
 // Streaming classify for descriptor layouts with owned windows (u8 LUT in LDS, or the u16 LUT
 // gathered from L2); stream_desc_lds: its dynamic LDS bytes (mode 0 read only, 1 in place, 2 records).
-int launch_classify_stream_desc(const ClassifyArgs& a, bool wide_lut, int grid, void* stream);
+int launch_classify_stream_desc(const ClassifyArgs& a, bool wide_lut, int mode, int grid, void* stream);
 size_t stream_desc_lds(uint32_t nb, int mode, bool wide_lut);
 // the tile-per-wave classify kernel (256 threads, one 64-packet tile per wave) over db.n descriptor
 // batches; a carries what they share (LUT, flags, lpm tables), db what differs

@@ -93,3 +93,124 @@ def test_group_plan_table(nb, source, n_pkts, head, n_parts):
     assert lib.nbg_debug_group_plan(nb, (C.c_uint64 * n)(*n_pkts), n, source, out) == 0
     assert tuple(out[:6]) == head
     assert list(out[6:]) == n_parts
+
+
+_ROUTE_ENV = ("NBG_STREAM", "NBG_SMALL", "NBG_STREAM_GRID", "NBG_GSCAN", "NBG_HIST_KERNEL_BINS")
+_SMALL, _TILED, _STREAM, _SDESC, _TPW = range(5)  # ClassifyKernel (nbgpu_internal.h)
+_SWAP, _LDS, _OWNED, _DEFER, _LUTT, _SD, _LAG = 0x1, 0x2, 0x4, 0x10, 0x20, 0x40, 0x80  # NBG_* flags
+_H65, _H1000 = (65, 65537), (1000, 655373)  # nb, M
+_F, _D, _O = 0, 1, 2  # layout: fixed slots, offsets + lengths, offsets only
+_M = 1048576
+
+
+def _route_row(handle, layout, n, flags, expect, stride=64, fixed_len=60, mac_out=False, chain=False, aligned=True,
+               capturing=False, ring=False, grouped=True, cus=256, grid_lds=256):
+    bits = mac_out * 1 | chain * 2 | aligned * 4 | capturing * 8 | ring * 16 | grouped * 32
+    return (handle, cus, grid_lds, layout, stride, fixed_len, n, flags, bits, expect)
+
+
+# the issue's table, row by row: handle, layout, n, flags -> the route's fields it names
+_ROUTES = [
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_STREAM, lean=1, win_owned=1, mode=1, tpw=8, grid=256, lag=0)),
+    _route_row(_H65, _F, 262144, _SWAP, dict(kernel=_STREAM, tpw=2)),
+    _route_row(_H65, _F, 262143, _SWAP, dict(kernel=_TPW, lds_lut=0, lean=1, tpw=1, grid=1024)),
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_TPW, lds_lut=0), ring=True),
+    _route_row((65, 65539), _F, _M, _SWAP, dict(kernel=_TPW)),
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_STREAM, mode=2), mac_out=True),
+    _route_row(_H65, _F, _M, 0, dict(kernel=_STREAM, mode=0)),
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_TPW, lean=0, win_owned=1), fixed_len=47),
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_TPW, lean=0), stride=72),
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_TPW, lean=0, win_owned=0), stride=48, fixed_len=48),
+    _route_row(_H65, _F, _M, _SWAP, dict(kernel=_TPW, lean=0), aligned=False),
+    _route_row(_H65, _F, _M, _SWAP | _LDS, dict(kernel=_TPW, lds_lut=1, tpw=4, grid=256), grid_lds=256),
+    _route_row(_H65, _F, _M, _SWAP | _LDS, dict(kernel=_TPW, lds_lut=0), ring=True),
+    _route_row(_H1000, _F, _M, _SWAP | _LDS, dict(kernel=_TPW, lds_lut=0)),  # 1,310,752 B > 72 KiB
+    _route_row(_H1000, _F, _M, _SWAP, dict(kernel=_TPW, lds_lut=0)),
+    _route_row(_H1000, _F, _M, _SWAP | _LUTT, dict(kernel=_TILED)),
+    _route_row(_H1000, _F, _M, _LUTT, dict(kernel=_TPW), chain=True),
+    _route_row(_H65, _F, 2048, _SWAP, dict(kernel=_SMALL)),
+    _route_row(_H65, _F, 2049, _SWAP, dict(kernel=_TPW)),
+    _route_row(_H65, _F, 100, _DEFER, dict(kernel=_TPW)),
+    _route_row(_H65, _F, 100, _LDS, dict(not_small=1)),
+    _route_row(_H65, _F, 100, _LUTT, dict(not_small=1)),
+    _route_row(_H65, _F, 100, 0, dict(not_small=1), chain=True),
+    _route_row(_H65, _F, 100, _SWAP, dict(not_small=1), aligned=False),
+    _route_row((1023, 65537), _F, 100, 0, dict(kernel=_SMALL)),
+    _route_row((1024, 65537), _F, 100, 0, dict(not_small=1)),  # 1025 bins
+    _route_row(_H65, _D, _M, _OWNED, dict(kernel=_TPW, win_owned=1, lean=0, fill_len=0)),
+    _route_row(_H65, _D, _M, _OWNED | _SD, dict(kernel=_SDESC, mode=0)),
+    _route_row(_H65, _D, _M, _OWNED | _SD | _SWAP, dict(kernel=_TPW)),  # in place does not fit with the u8 LUT
+    _route_row(_H65, _D, _M, _OWNED | _SD | _SWAP, dict(kernel=_SDESC, mode=2), mac_out=True),
+    _route_row(_H65, _D, _M, _OWNED | _SD, dict(kernel=_SDESC, mode=0), chain=True),
+    _route_row(_H1000, _D, _M, _OWNED | _SD | _SWAP, dict(kernel=_SDESC, mode=1)),
+    _route_row(_H1000, _D, _M, _OWNED | _SD, dict(kernel=_TPW), chain=True),
+    _route_row(_H65, _D, _M, _SD, dict(kernel=_TPW)),
+    _route_row(_H65, _D, 262143, _OWNED | _SD, dict(kernel=_TPW)),
+    _route_row(_H65, _O, _M, 0, dict(kernel=_TPW, fill_len=1)),
+    _route_row(_H65, _O, 2048, 0, dict(kernel=_SMALL, fill_len=0)),
+    # captured: classify_common refuses a route that needs the length fill ("pass d_len to capture ...")
+    _route_row(_H65, _O, _M, 0, dict(kernel=_TPW, fill_len=1), capturing=True),
+    _route_row(_H65, _F, _M, _SWAP | _LAG, dict(kernel=_STREAM, lag=1)),
+    _route_row(_H65, _F, _M, _SWAP | _LAG, dict(kernel=_STREAM, lag=0), cus=128),  # 256 partitions > 128 blocks
+    _route_row(_H65, _F, _M, _SWAP | _LAG, dict(lag=0), grouped=False),
+    _route_row(_H65, _F, _M, _SWAP | _LAG | _LUTT, dict(kernel=_STREAM, lag=0)),
+    _route_row((256, 65537), _F, 524288, _SWAP | _LAG, dict(kernel=_STREAM, lag=0)),  # 257 bins: hist_kernel rows
+    _route_row((187, 65537), _F, 524288, _SWAP | _LAG, dict(lag=1)),  # 163,488 B of LDS
+    _route_row((188, 65537), _F, 524288, _SWAP | _LAG, dict(lag=0)),  # 163,872 B > 160 KiB
+    _route_row((255, 65537), _F, 524288, _SWAP | _LAG, dict(lag=1), mac_out=True),  # mode 2 rows are 48 B
+    _route_row((187, 65537), _F, _M, _SWAP | _LAG, dict(lag=0)),  # 188 x 256 row entries > 32,768: scan kernel
+]
+
+
+@pytest.mark.parametrize("handle,cus,grid_lds,layout,stride,fixed_len,n,flags,bits,expect", _ROUTES,
+                         ids=[str(i + 1) for i in range(len(_ROUTES))])
+def test_classify_route_table(handle, cus, grid_lds, layout, stride, fixed_len, n, flags, bits, expect):
+    """The classify route every launch site takes (classify_route.cpp), pinned at the edges of its
+    rules: 2,048 packets (small kernel), 262,144 (streaming), M <= 65537, 256 / 257 bins, a
+    persistent ring on the device, the fixed-slot rule, the write mode, the descriptor streaming
+    modes, the length fill, and the lagged launch's partition, scan and 160 KiB LDS bounds."""
+    import os
+
+    from netbricks_amd._lib import lib
+
+    if any(e in os.environ for e in _ROUTE_ENV):
+        pytest.skip("NBG_STREAM / NBG_SMALL / NBG_STREAM_GRID / NBG_GSCAN / NBG_HIST_KERNEL_BINS override the rules")
+    out = (C.c_uint32 * 9)()
+    nb, m = handle
+    assert lib.nbg_debug_classify_route(nb, m, cus, grid_lds, 1, layout, stride, fixed_len, n, flags, bits, out) == 0
+    got = dict(zip(("kernel", "lds_lut", "win_owned", "lean", "fill_len", "lag", "mode", "tpw", "grid"), out))
+    got["not_small"] = int(got["kernel"] != _SMALL)
+    assert {k: got[k] for k in expect} == expect
+
+
+# handle, batch sizes, fused; stride 64, fixed_len 60, aligned, no ring, grouped unless said
+_FUSED = [
+    (_H65, [131072, 131072], {}, 1),
+    (_H65, [131072, 131071], {}, 0),
+    (_H65, [262144, 0], {}, 0),  # an empty batch
+    (_H65, [131072, 131072], dict(stride=72), 0),
+    (_H65, [131072, 131072], dict(stride=48), 0),
+    (_H65, [131072, 131072], dict(ring=True), 0),
+    ((255, 65537), [524288, 524288], {}, 1),  # 256 bins x 128 partitions = 32,768: direct scan
+    ((255, 65537), [1048576, 1048576], {}, 0),  # scan kernel
+    ((255, 65537), [1048576, 1048576], dict(grouped=False), 1),
+    ((256, 65537), [524288, 524288], {}, 0),  # 257 bins
+]
+
+
+@pytest.mark.parametrize("handle,sizes,extras,fused", _FUSED, ids=[str(i + 1) for i in range(len(_FUSED))])
+def test_multi_fused_table(handle, sizes, extras, fused):
+    """nbg_maglev_classify_device_multi's fused rule (classify_route.cpp multi_fused): lean slots in
+    every batch, none empty, 262,144 packets in all, at most 256 bins, no ring, and a grouping that
+    scans directly."""
+    import os
+
+    from netbricks_amd._lib import lib
+
+    if any(e in os.environ for e in _ROUTE_ENV):
+        pytest.skip("NBG_STREAM / NBG_SMALL / NBG_STREAM_GRID / NBG_GSCAN / NBG_HIST_KERNEL_BINS override the rules")
+    bits = 4 | extras.get("ring", False) * 16 | extras.get("grouped", True) * 32
+    n = len(sizes)
+    nb, m = handle
+    got = lib.nbg_debug_multi_fused(nb, m, 256, (C.c_uint64 * n)(*sizes), n, extras.get("stride", 64), 60, bits)
+    assert got == fused
