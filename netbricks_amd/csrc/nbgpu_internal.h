@@ -365,12 +365,25 @@ struct HostRingArgs {
   uint32_t slots;           // power of two
   uint64_t idle_ticks;      // 100 MHz wall clock
 };
-int launch_host_ring(const HostRingArgs& r, uint32_t blocks, void* stream);
-uint32_t small_variant(bool wide_lut, uint32_t m, uint32_t nb, bool win32);
 
+// Launchers and their sizing helpers, by the file that defines them.  `wide_lut` = u16 entries;
+// `lds_lut` = stage in LDS.
 
-// Launchers (maglev_kernels.hip).  `wide_lut` = u16 entries; `lds_lut` = stage in LDS.
+// classify_tile.hip
 int launch_classify(const ClassifyArgs& a, bool wide_lut, bool lds_lut, int grid, void* stream);
+// the tile-per-wave classify kernel (256 threads, one 64-packet tile per wave) over db.n descriptor
+// batches; a carries what they share (LUT, flags, lpm tables), db what differs
+int launch_classify_desc_multi(const ClassifyArgs& a, const DescBatches& db, bool wide_lut, void* stream);
+uint32_t classify_block_pkts();  // packets per block and tile per wave of launch_classify_desc_multi
+int launch_zero(uint32_t* p, size_t words, void* stream);  // p[0, words) = 0 (one kernel)
+int launch_lpm_lookup(const uint16_t* tbl24, const uint16_t* tbl_long, const uint32_t* ips, uint64_t n,
+                      uint16_t* gate, void* stream);
+int launch_classify_idx(const ClassifyArgs& a, int grid, void* stream);  // kIdx classify (tile per wave)
+int launch_tiled_lookup(const TileArgs& a, void* stream);
+uint32_t lut_tiles(uint64_t m);
+int classify_grid(bool lds_lut, uint32_t lut_bytes, uint32_t nb, int device, int* grid);
+
+// classify_stream.hip
 // Streaming classify (lean fixed slots, u8 LUT of <= 65537 entries staged in LDS): one block per
 // CU; a.tiles_per_wave = the contiguous 64-packet tiles of each of the grid's waves; mode: the
 // route's (0 read only, 1 in place, 2 records).
@@ -394,31 +407,28 @@ int stream_waves_per_block();
 // gathered from L2); stream_desc_lds: its dynamic LDS bytes (mode 0 read only, 1 in place, 2 records).
 int launch_classify_stream_desc(const ClassifyArgs& a, bool wide_lut, int mode, int grid, void* stream);
 size_t stream_desc_lds(uint32_t nb, int mode, bool wide_lut);
-// the tile-per-wave classify kernel (256 threads, one 64-packet tile per wave) over db.n descriptor
-// batches; a carries what they share (LUT, flags, lpm tables), db what differs
-int launch_classify_desc_multi(const ClassifyArgs& a, const DescBatches& db, bool wide_lut, void* stream);
-uint32_t classify_block_pkts();  // packets per block and tile per wave of launch_classify_desc_multi
-int launch_zero(uint32_t* p, size_t words, void* stream);  // p[0, words) = 0 (one kernel)
-bool hist_in_classify(uint32_t nbins);  // group_plan.cpp
-int launch_lpm_lookup(const uint16_t* tbl24, const uint16_t* tbl_long, const uint32_t* ips, uint64_t n,
-                      uint16_t* gate, void* stream);
-// The plan's launches: hist (p.hist_kernel), scan (p.scan == kScanKernel), then group_wide (p.wide)
-// or one group launch over p.gm.g[0 .. p.n).  More than 16,383 bins (hist rows past 64 KiB of LDS)
-// and the wide path take one batch only.
-// compact: the LDS-light group kernel (group_compact(): many bins while a persistent ring runs)
-int launch_group_plan(const GroupPlan& p, void* stream, bool compact);
-bool group_compact(uint32_t nbins, bool ring_running);
+
+// small.hip
 // One launch for a batch of at most small_max() packets and at most kMaxGroupBins bins: classify
 // and (when g.perm / g.counts) group.  The batch base must be 16-B aligned.
 // done (nullable): completion word the kernel sets to done_val once its outputs are visible to the host
 int launch_small(const ClassifyArgs& a, const GroupArgs& g, bool wide_lut, void* stream, uint32_t* done = nullptr,
                  uint32_t done_val = 0);
 uint32_t small_max();
-int launch_classify_idx(const ClassifyArgs& a, int grid, void* stream);  // kIdx classify (tile per wave)
-int launch_tiled_lookup(const TileArgs& a, void* stream);
-uint32_t lut_tiles(uint64_t m);
+int launch_host_ring(const HostRingArgs& r, uint32_t blocks, void* stream);
+uint32_t small_variant(bool wide_lut, uint32_t m, uint32_t nb, bool win32);
+
+// group.hip
+// The plan's launches: hist (p.hist_kernel), scan (p.scan == kScanKernel), then group_wide (p.wide)
+// or one group launch over p.gm.g[0 .. p.n).  More than 16,383 bins (hist rows past 64 KiB of LDS)
+// and the wide path take one batch only.
+// compact: the LDS-light group kernel (group_compact(): many bins while a persistent ring runs)
+int launch_group_plan(const GroupPlan& p, void* stream, bool compact);
+bool group_compact(uint32_t nbins, bool ring_running);
 size_t group_lds(uint32_t nbins, bool compact);
-int pick_group_scan(uint32_t nbins, uint32_t n_parts);  // group_plan.cpp
-int classify_grid(bool lds_lut, uint32_t lut_bytes, uint32_t nb, int device, int* grid);
+
+// group_plan.cpp
+bool hist_in_classify(uint32_t nbins);
+int pick_group_scan(uint32_t nbins, uint32_t n_parts);
 
 }  // namespace nbg

@@ -40,7 +40,7 @@ def test_host_submit_rejects_length_mismatch():
 
 def test_compact_group_block_fits_beside_ring():
     """The grouping beside a running in-place ring takes the compact group kernel when the default
-    block would not fit in the LDS the ring leaves (maglev_kernels.hip group_compact): the compact
+    block would not fit in the LDS the ring leaves (group.hip group_compact): the compact
     block must fit there for every bin count the group kernels take (<= 1024 bins; above 1023
     backends group_wide_kernel runs), and the default block must fit for C2's 66 bins."""
     from netbricks_amd._lib import lib
@@ -53,6 +53,23 @@ def test_compact_group_block_fits_beside_ring():
     assert lib.nbg_debug_group_lds(1001, 0) > budget  # C3 beside a ring: the compact kernel
     assert lib.nbg_debug_set_group_compact(2) != 0
     assert lib.nbg_debug_set_group_compact(-1) == 0
+
+
+@pytest.mark.parametrize("nbins,compact,lds", [
+    (66, 0, 22368),
+    (129, 0, 19616),
+    (1001, 0, 40544),
+    (1001, 1, 28176),
+    (1024, 1, 28800),
+])
+def test_group_lds_pinned(nbins, compact, lds):
+    """group_lds() (group.hip) is a hand-written mirror of the LDS carve-up at the top of group_kernel
+    and group_direct_kernel: its bytes are pinned at C2's 66 bins (with the peer table), the first bin
+    count without it, C3's 1001 bins on both kernels and the compact kernel's largest, so that a slip
+    in the size function fails here and not as a kernel writing past its dynamic LDS."""
+    from netbricks_amd._lib import lib
+
+    assert lib.nbg_debug_group_lds(nbins, compact) == lds
 
 
 _DIRECT, _KERNEL = 2, 0  # GroupScan (nbgpu_internal.h)

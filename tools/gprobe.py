@@ -54,8 +54,7 @@ def patch(src):
     beg = src.index("void group_kernel(GroupMulti gm) {")
     end = src.index("// group_direct_kernel:")
     g = src[beg:end]
-    g = _insert(g, "  const uint32_t c = blockIdx.x - bj * gm.per;  // partition of batch bj\n",
-                "  NBG_GW(0);\n  NBG_GP(0);\n", before=False)
+    g = _insert(g, "  const uint32_t c_lin = blockIdx.x - bj * gm.per;\n", "  NBG_GW(0);\n  NBG_GP(0);\n", before=False)
     g = _insert(g, "  const unsigned long long lt = (lane == 0)", "  NBG_GP(1);\n")
     g = _insert(g, "  if (perm) rank_chunk(pbeg);\n", "  NBG_GP(2);\n", before=False)
     g = _insert(g, "  lds_sync();  // (B1) base / tot zeroed, every wave's counts of the first chunk in LDS\n",
@@ -82,7 +81,7 @@ def build():
     shutil.copytree(os.path.join(ROOT, "netbricks_amd", "csrc"), os.path.join(SRC, "netbricks_amd", "csrc"),
                     ignore=shutil.ignore_patterns("*.o", "*.s"))
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(SRC, "include"))
-    kf = os.path.join(SRC, "netbricks_amd", "csrc", "maglev_kernels.hip")
+    kf = os.path.join(SRC, "netbricks_amd", "csrc", "group.hip")
     with open(kf) as f:
         s = f.read()
     with open(kf, "w") as f:
